@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Headline benchmark: clips/sec of LLark's audio-encoder -> LLM forward on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  A plain run prints the headline line only; --full adds the rooflines, CPU baseline, other precisions, parity checks and extra legs.
   N > 1 works both ways: started plainly (no WORLD_SIZE in the environment) it launches its own N ranks, one per GPU,
   under torch.distributed.run (like scripts/training/train_llark.sh:20-22 of the reference); started BY
   ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`` it is one of those ranks.
@@ -558,6 +559,29 @@ def extra_mpt(args, device, steps: int = 3, new_tokens: int = 64):
     return out
 
 
+DUMP_NAMES = {"e2e": "logits", "llama": "logits", "jukebox": "embeddings", "generate": "tokens", "mpt": "tokens", "clap": "embeddings",
+              "train": "loss", "mpt-train": "loss"}
+DUMP_BYTES = 48 << 20          # --dump-outputs writes at most this much (logits of the e2e step alone are 380 MB)
+
+
+def dump_outputs(out, directory, name):
+    """--dump-outputs: what the last timed step returned (the logits of the Llama forward, the embeddings, the generated tokens or
+    the training loss), as ``directory/<name>.npy`` -- float32, or float64 for integer outputs (exact).  An output larger than
+    DUMP_BYTES is written as a fixed sample of its rows (last axis whole, rows drawn with seed 0, in order), and the flat row
+    indices of the sample go to ``<name>_rows.npy``.  Every input of the step is seeded, so runs with the same arguments can be
+    compared array for array."""
+    os.makedirs(directory, exist_ok=True)
+    t = out.detach()
+    t = t.float() if t.is_floating_point() else t.double()
+    if t.numel() * t.element_size() > DUMP_BYTES:
+        rows = t.reshape(-1, t.shape[-1])
+        n = max(1, DUMP_BYTES // (rows.shape[1] * t.element_size()))
+        idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], size=min(n, rows.shape[0]), replace=False))
+        np.save(os.path.join(directory, name + "_rows.npy"), idx.astype(np.float64))
+        t = rows[torch.from_numpy(idx).to(rows.device)]
+    np.save(os.path.join(directory, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -590,7 +614,16 @@ def main():
                          "chosen one, `alt_prior_precision` the other")
     ap.add_argument("--llm-precision", default="split", choices=["split", "bf16"],
                     help="Llama half: fp32-class bf16 hi+lo (default, matches the fp32 reference path) or single-pass bf16")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: per-kernel HIP events in the timed region (roofline, "
+                         "kernel_ms), CPU-oracle baseline, the other prior / Llama precision with its parity pair, VQ code check, "
+                         "and the generate / MPT / train legs of the e2e line.  Without it a run only sets up, warms up, times "
+                         "--steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if not args.batch:
         args.batch = {"train": 4, "mpt-train": 4, "generate": 1, "clap": 64}.get(args.stages, 8)
 
@@ -630,23 +663,30 @@ def main():
         for _ in range(args.warmup):
             step()
         _barrier(world)
-        # Per-op HIP events are recorded inside the timed region (they are where `roofline` comes from) -- except for `generate` / `mpt`,
-        # whose decode steps are ~160 small launches per token: there the events alone cost ~0.8 ms per token (4.8 vs 4.0 ms,
-        # scripts/bench_decode.py), so the timed region runs uninstrumented and the per-kernel breakdown comes from a second,
-        # identical pass.
-        events_in_timed = args.stages not in ("generate", "mpt")
+        # With --full, per-op HIP events are recorded inside the timed region (they are where `roofline` comes from) -- except for
+        # `generate` / `mpt`, whose decode steps are ~160 small launches per token: there the events alone cost ~0.8 ms per token
+        # (4.8 vs 4.0 ms, scripts/bench_decode.py), so the timed region runs uninstrumented and the per-kernel breakdown comes from a
+        # second, identical pass.  A plain run records no per-op events.
+        events_in_timed = args.full and args.stages not in ("generate", "mpt")
         if events_in_timed:
             ops.start_kernel_timing()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
+        for i in range(args.steps):
+            if i + 1 < args.steps:
+                step()
+            else:
+                out = step()                          # kept for --dump-outputs; earlier steps' results are dropped as before
         torch.cuda.synchronize()
         mine = time.perf_counter() - t0               # this rank's own K steps (before waiting for the others)
         _barrier(world)
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:           # before anything else runs on the engines whose buffers `out` may view
+            dump_outputs(out, args.dump_outputs, DUMP_NAMES[args.stages])
+        del out
+        timers = {}
         if events_in_timed:
             timers = ops.stop_kernel_timing()
-        else:
+        elif args.full:
             ops.start_kernel_timing()
             for _ in range(args.steps):
                 step()
@@ -663,23 +703,6 @@ def main():
     if rank == 0:
         clips = args.batch * world * args.steps
         value = clips / elapsed
-        # dominant kernel: the split-fp16 MFMA GEMM of the prior.  Algorithmic flops (2*M*N*K of the
-        # fp32-equivalent product; the hi/lo second pass is NOT counted) / HIP-event time of its launches.
-        roof = None
-        if args.stages != "llama" and enc is not None and prior_roofline(timers, hps, args, args.prior_precision) is not None:
-            roof = prior_roofline(timers, hps, args, args.prior_precision)
-        elif args.stages == "clap":
-            roof = roofline_clap(timers, args, llm)
-        elif llm is not None and args.stages not in ("mpt", "mpt-train"):
-            roof = llm.roofline(timers, args)
-        cpu = None
-        if not args.no_cpu_baseline and world == 1 and args.stages not in ("mpt", "mpt-train"):
-            if args.stages == "clap":
-                cpu = cpu_baseline_clap(llm)
-            elif args.stages == "train":
-                cpu = cpu_baseline_train(args)
-            else:
-                cpu = cpu_baseline(hps, weights, args)
         workload = {"e2e": "configs[1]+llm: 8x25s clips -> Jukebox VQ-VAE+36-layer prior -> 240x4800 -> projector -> Llama-2-7B fwd (S=371) logits",
                     "jukebox": "configs[1]: Jukebox encoder+prior forward, batch=8x25s clips -> (240,4800) embeddings",
                     "llama": "projector + Llama-2-7B forward (S=371) on precomputed embeddings",
@@ -714,11 +737,34 @@ def main():
                        "prior_layernorm_folded": getattr(args, "prior_ln_fold", None) if args.stages in ("e2e", "jukebox", "generate") else None,
                        "parallelism": f"dp{world} (clip-sharded, no collective)" if args.stages != "train" else f"dp{world} (clip-sharded, RCCL all-reduce of fp32 gradients ({args.grad_comm} on the links) once per optimizer step)",
                        "debug_overrides": bool(args.depth or args.tiny)},
+        }
+        if not args.full:
+            print(json.dumps(line), flush=True)
+
+    if rank == 0 and args.full:
+        # dominant kernel: the split-fp16 MFMA GEMM of the prior.  Algorithmic flops (2*M*N*K of the
+        # fp32-equivalent product; the hi/lo second pass is NOT counted) / HIP-event time of its launches.
+        roof = None
+        if args.stages != "llama" and enc is not None and prior_roofline(timers, hps, args, args.prior_precision) is not None:
+            roof = prior_roofline(timers, hps, args, args.prior_precision)
+        elif args.stages == "clap":
+            roof = roofline_clap(timers, args, llm)
+        elif llm is not None and args.stages not in ("mpt", "mpt-train"):
+            roof = llm.roofline(timers, args)
+        cpu = None
+        if not args.no_cpu_baseline and world == 1 and args.stages not in ("mpt", "mpt-train"):
+            if args.stages == "clap":
+                cpu = cpu_baseline_clap(llm)
+            elif args.stages == "train":
+                cpu = cpu_baseline_train(args)
+            else:
+                cpu = cpu_baseline(hps, weights, args)
+        line.update({
             "roofline": roof, "roofline_conv": conv_roofline(timers, args),
             "roofline_llm": (llm.roofline(timers, args) if llm is not None and args.stages not in ("train", "mpt", "mpt-train", "clap") else None),
             "cpu_baseline": cpu,
             "kernel_ms": {k: round(v[1] / args.steps, 3) for k, v in timers.items()},
-        }
+        })
         if args.stages == "llama" and line.get("roofline_llm") and line["roofline_llm"].get("whole_forward_flops_t"):
             line["roofline_llm"]["whole_forward_frac"] = round(line["roofline_llm"]["whole_forward_flops_t"] / (elapsed / args.steps) / PEAK_F16_MFMA_TFLOPS, 4)
         if args.stages in ("generate", "mpt"):
