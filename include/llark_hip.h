@@ -479,6 +479,25 @@ int llark_l2_normalize_rows(float* x, int ldx, int rows, int width, float eps, l
 int llark_attn_decode_rope_bf16(const float* qkv, int batch, int nh, int hd, int pos, const int* pos_dev, const float* cos_t,
                                 const float* sin_t, int max_pos, void* k_cache, void* vt_cache, void* k_cache_lo, void* vt_cache_lo,
                                 int smax, void* out, void* out_lo, const float* alibi_slopes, llark_stream_t stream);
+/* Ragged decode over batch slots (every sequence its own cache length; in-flight slot refill):
+ *   llark_attn_decode_rope_bf16_rows: llark_attn_decode_rope_bf16 with the position of sequence b read from pos_rows[b]
+ *     (int32 [batch], device): block (h, b) rotates q / k with cos / sin[pos_rows[b]], appends k and v at row pos_rows[b] of slot
+ *     b and walks keys 0 .. pos_rows[b].  pos_rows[b] < 0 marks an idle slot: nothing is written to its caches, its output head
+ *     is zero (a position >= smax is treated the same way).  Caches k [batch][nh][smax][128], v^T [batch][nh][128][smax];
+ *     out bf16 [batch][nh * 128]; dynamic LDS holds smax scores; smax <= max_pos (rows of cos_t / sin_t [max_pos][64]).
+ *   llark_decode_advance_rows: the bookkeeping after the logits of such a step, one launch.  logits fp32 [batch][ldl];
+ *     state int32 [batch] of LLARK_ROW_*; for every ACTIVE row: token = choice[b] when choice != NULL, else the first maximal
+ *     index of logits[b][0 .. vocab) (torch.argmax); next_ids[b] = token (int64), out_col[b * ld_out] = token (out_col may be
+ *     NULL); state[b] = LLARK_ROW_FINISHED when token == eos (eos >= 0); pos_rows[b] += 1 (pos_rows may be NULL: no advance).
+ *     IDLE and FINISHED rows get `pad` in next_ids / out_col and keep their position. */
+#define LLARK_ROW_IDLE 0
+#define LLARK_ROW_ACTIVE 1
+#define LLARK_ROW_FINISHED 2
+int llark_attn_decode_rope_bf16_rows(const float* qkv, int batch, int nh, int hd, const int* pos_rows, const float* cos_t,
+                                     const float* sin_t, int max_pos, void* k_cache, void* vt_cache, void* k_cache_lo, void* vt_cache_lo,
+                                     int smax, void* out, void* out_lo, const float* alibi_slopes, llark_stream_t stream);
+int llark_decode_advance_rows(const float* logits, int ldl, int vocab, int batch, const int64_t* choice, int* pos_rows, int* state,
+                              int64_t* next_ids, int64_t* out_col, int ld_out, int64_t eos, int64_t pad, llark_stream_t stream);
 /* Decode-step forms with the sequence position in DEVICE memory (*pos_dev = tokens already cached = position of the
  * new token; s = 1): lets ONE captured hipGraph of the whole decode step serve every generated token of
  * m2t/models/llamav2.py:339-365 / m2t/infer.py:137-148. */

@@ -628,7 +628,9 @@ static void launch_attn_prefill(hipStream_t st, const bf16_t* q, const bf16_t* k
 // x 8 keys x UBT the same per round of the V pass: with the 25 s prompt (371 + up to 64 keys) UBT = 8 walks each pass in ONE round of memory
 // latency instead of two (round 6).  UBT = 4 at 16 waves is capped at 72 registers so that the workgroup fits a CU next to a chained o_proj
 // workgroup (llark_attn_decode_rope_bf16_chain: 4 x 72 + 2 x 104 of 512 registers per SIMD lane).
-template <int NW, int UBT>
+// ROWS: `pos_dev` is pos_rows[batch], one position per sequence (llark_attn_decode_rope_bf16_rows: ragged decode over batch slots);
+// a slot whose position is < 0 (idle) or >= smax writes nothing to the caches and zeros to its output head.
+template <int NW, int UBT, bool ROWS = false>
 __global__ __launch_bounds__(NW * 64, (NW >= 16 && UBT == 4) ? 7 : 1) void attn_decode_kernel(const bf16_t* __restrict__ q, bf16_t* kc, bf16_t* vtc,
                                                               const bf16_t* __restrict__ q_lo, bf16_t* kc_lo, bf16_t* vtc_lo,
                                                               bf16_t* __restrict__ out, bf16_t* __restrict__ out_lo,
@@ -643,7 +645,15 @@ __global__ __launch_bounds__(NW * 64, (NW >= 16 && UBT == 4) ? 7 : 1) void attn_
     constexpr int UB = UBT;                       // loads in flight per lane
     constexpr int PARTS = NT / 128;               // threads sharing one output dim in the PV pass
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (pos_dev) total = *pos_dev + 1;            // graph-captured decode: keys 0..pos are visible
+    if constexpr (ROWS) {
+        const int p = pos_dev[blockIdx.y];                       // uniform per block: the whole block leaves together
+        if (p < 0 || p >= smax) {
+            if (threadIdx.x < 128)
+                store_split(out, out_lo, (size_t)blockIdx.y * (nh * 128) + blockIdx.x * 128 + threadIdx.x, 0.0f);
+            return;
+        }
+        total = p + 1;
+    } else if (pos_dev) total = *pos_dev + 1;     // graph-captured decode: keys 0..pos are visible
     float* sp = (float*)smem;                    // [total] scores / probabilities
     __shared__ float sq[128];
     __shared__ float red[2 * NW];
@@ -785,19 +795,20 @@ __global__ __launch_bounds__(NW * 64, (NW >= 16 && UBT == 4) ? 7 : 1) void attn_
 #define ATTN_DECODE_WIDE 0        // 1: 8 loads in flight per lane at 16 waves beyond 256 keys -- measured in round 6 (profiles/r06_decode_attn_ub_ab.txt): no gain (302.9 vs 302.1 ms per clip), off
 #endif
 // `keys`: how many keys the walk may see (the host position + 1, or smax when the position lives in device memory)
-template <typename... Args>
+template <bool ROWS = false, typename... Args>
 static void launch_attn_decode(int nh, int batch, size_t lds, hipStream_t s, int keys, bool chained, Args... args) {
     dim3 grid(nh, batch);
     if ((long)nh * batch < 256) {
-        if (ATTN_DECODE_WIDE && keys > 256 && !chained) attn_decode_kernel<16, 8><<<grid, 1024, lds, s>>>(args...);
-        else attn_decode_kernel<16, 4><<<grid, 1024, lds, s>>>(args...);
-    } else attn_decode_kernel<4, 8><<<grid, 256, lds, s>>>(args...);
+        if (ATTN_DECODE_WIDE && keys > 256 && !chained) attn_decode_kernel<16, 8, ROWS><<<grid, 1024, lds, s>>>(args...);
+        else attn_decode_kernel<16, 4, ROWS><<<grid, 1024, lds, s>>>(args...);
+    } else attn_decode_kernel<4, 8, ROWS><<<grid, 256, lds, s>>>(args...);
 }
 
+template <bool ROWS = false>
 static void attn_decode_lds_limit(int lds) {
-    (void)hipFuncSetAttribute((const void*)attn_decode_kernel<4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)attn_decode_kernel<16, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)attn_decode_kernel<16, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)attn_decode_kernel<4, 8, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)attn_decode_kernel<16, 4, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)attn_decode_kernel<16, 8, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 }
 
 
@@ -852,6 +863,66 @@ __global__ __launch_bounds__(256) void ce_reduce_kernel(const float* __restrict_
         __syncthreads();
     }
     if (threadIdx.x == 0) { out[0] = scnt[0] > 0 ? ssum[0] / (float)scnt[0] : NAN; out[1] = (float)scnt[0]; }
+}
+
+// ------------------------------------------------------------------------------------------
+// Greedy bookkeeping of one ragged decode step (llark_decode_advance_rows): one block per slot.  An ACTIVE row takes
+// torch.argmax of its logits (first maximal index; NaN counts as the maximum, as in torch) or choice[b] when given, writes it
+// to next_ids[b] and out_col[b * ld_out], turns FINISHED on eos and advances pos_rows[b]; IDLE and FINISHED rows emit `pad`.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool argmax_better(float v, int i, float bv, int bi) {
+    const bool vn = v != v, bn = bv != bv;
+    if (vn || bn) return vn && (!bn || i < bi);
+    return v > bv || (v == bv && i < bi);
+}
+
+__global__ __launch_bounds__(256) void decode_advance_rows_kernel(const float* __restrict__ logits, int ldl, int vocab,
+                                                                   const long long* __restrict__ choice, int* pos_rows, int* state,
+                                                                   long long* __restrict__ next_ids, long long* __restrict__ out_col,
+                                                                   int ld_out, long long eos, long long pad) {
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int st = state[b];
+    __syncthreads();                                   // every wave has read the state before thread 0 may change it
+    if (st != LLARK_ROW_ACTIVE) {
+        if (tid == 0) {
+            next_ids[b] = pad;
+            if (out_col) out_col[(size_t)b * ld_out] = pad;
+        }
+        return;
+    }
+    long long tok;
+    if (choice) {
+        tok = choice[b];
+    } else {
+        const float* row = logits + (size_t)b * ldl;
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+        for (int j = tid; j < vocab; j += 256) {
+            const float v = row[j];
+            if (argmax_better(v, j, bv, bi)) bv = v, bi = j;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(bv, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            if (argmax_better(ov, oi, bv, bi)) bv = ov, bi = oi;
+        }
+        if (lane == 0) sv[wv] = bv, si[wv] = bi;
+        __syncthreads();
+        bv = sv[0], bi = si[0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w)
+            if (argmax_better(sv[w], si[w], bv, bi)) bv = sv[w], bi = si[w];
+        tok = bi;
+    }
+    if (tid == 0) {
+        next_ids[b] = tok;
+        if (out_col) out_col[(size_t)b * ld_out] = tok;
+        if (eos >= 0 && tok == eos) state[b] = LLARK_ROW_FINISHED;
+        if (pos_rows) pos_rows[b] += 1;
+    }
 }
 
 }  // namespace llark
@@ -1073,4 +1144,41 @@ extern "C" int llark_attn_decode_rope_bf16_chain(const float* qkv, int batch, in
     LLARK_REQUIRE(done, "attn_decode_rope_chain: null counter");
     return attn_decode_rope_impl(qkv, batch, nh, hd, pos, pos_dev, cos_t, sin_t, max_pos, k_cache, vt_cache, k_cache_lo, vt_cache_lo, smax, out,
                                  out_lo, alibi_slopes, done, stream);
+}
+
+// Ragged decode step over batch slots: llark_attn_decode_rope_bf16 with the position of sequence b read from pos_rows[b] (idle slot: < 0).
+// Dynamic LDS is sized for smax keys, as in llark_attn_decode_bf16_dpos; the wave count follows nh * batch (launch_attn_decode).
+extern "C" int llark_attn_decode_rope_bf16_rows(const float* qkv, int batch, int nh, int hd, const int* pos_rows, const float* cos_t,
+                                                const float* sin_t, int max_pos, void* k_cache, void* vt_cache, void* k_cache_lo,
+                                                void* vt_cache_lo, int smax, void* out, void* out_lo, const float* alibi_slopes,
+                                                llark_stream_t stream) {
+    LLARK_REQUIRE(qkv && pos_rows && cos_t && sin_t && k_cache && vt_cache && out, "attn_decode_rope_rows: null pointer");
+    LLARK_REQUIRE(hd == 128, "attn_decode_rope_rows: head_dim must be 128 (Llama-2), got %d", hd);
+    LLARK_REQUIRE((k_cache_lo == nullptr) == (vt_cache_lo == nullptr) && (k_cache_lo == nullptr) == (out_lo == nullptr),
+                  "attn_decode_rope_rows: give all lo planes (fp32-class mode) or none");
+    LLARK_REQUIRE(batch > 0 && nh > 0 && smax > 0 && smax % 8 == 0 && smax <= max_pos,
+                  "attn_decode_rope_rows: bad shape batch=%d smax=%d max_pos=%d", batch, smax, max_pos);
+    const float scale = (float)(1.0 / sqrt((double)hd));
+    const size_t lds = (size_t)smax * sizeof(float);
+    LLARK_REQUIRE(lds <= 128 * 1024, "attn_decode_rope_rows: cache length %d too long for the LDS score buffer", smax);
+    static int attr_lds = 0;
+    if ((int)lds > 48 * 1024 && (int)lds > attr_lds) {
+        attn_decode_lds_limit<true>((int)lds);
+        attr_lds = (int)lds;
+    }
+    launch_attn_decode<true>(nh, batch, lds, (hipStream_t)stream, smax, false, (const bf16_t*)nullptr, (bf16_t*)k_cache, (bf16_t*)vt_cache,
+                             (const bf16_t*)nullptr, (bf16_t*)k_cache_lo, (bf16_t*)vt_cache_lo, (bf16_t*)out, (bf16_t*)out_lo, nh, 1, smax,
+                             scale, pos_rows, alibi_slopes, qkv, cos_t, sin_t, (unsigned*)nullptr);
+    return check_launch("attn_decode_rope_rows");
+}
+
+extern "C" int llark_decode_advance_rows(const float* logits, int ldl, int vocab, int batch, const int64_t* choice, int* pos_rows, int* state,
+                                         int64_t* next_ids, int64_t* out_col, int ld_out, int64_t eos, int64_t pad, llark_stream_t stream) {
+    LLARK_REQUIRE(state && next_ids && (logits || choice), "decode_advance_rows: null pointer");
+    LLARK_REQUIRE(batch > 0 && vocab > 0 && (choice || ldl >= vocab) && (!out_col || ld_out >= 1),
+                  "decode_advance_rows: bad shape batch=%d vocab=%d ldl=%d ld_out=%d", batch, vocab, ldl, ld_out);
+    decode_advance_rows_kernel<<<batch, 256, 0, (hipStream_t)stream>>>(logits, ldl, vocab, (const long long*)choice, pos_rows, state,
+                                                                      (long long*)next_ids, (long long*)out_col, ld_out, (long long)eos,
+                                                                      (long long)pad);
+    return check_launch("decode_advance_rows");
 }

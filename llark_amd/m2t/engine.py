@@ -138,6 +138,9 @@ class HipLlamaEngine:
         self._resident_wgs = None
         self._rope_rows = None                                      # gather index of the epilogue's q|k|v row order (built on first use)
         self._dec: Dict[int, dict] = {}
+        # ragged mode (init_slots / prefill_slots / decode_slots): every batch slot has its own cache length
+        self._slot_ws = None
+        self._clear_slots()
 
     # ---- weights -------------------------------------------------------------------------------
     def _bf16(self, t: torch.Tensor) -> torch.Tensor:
@@ -251,25 +254,28 @@ class HipLlamaEngine:
     def _workspace(self, batch: int, s: int):
         key = (batch, s)
         if self._ws_key != key:
-            d, dev = self.dims, self.device
-            rows = batch * s
-            H, I = d.hidden_size, d.intermediate_size
-            ws = {
-                "h": torch.empty((rows, H), dtype=torch.float32, device=dev),
-                "x16": torch.empty((rows, H), dtype=torch.bfloat16, device=dev),
-                "qkv": torch.empty((rows, 3 * H), dtype=torch.float32, device=dev),
-                "q": torch.empty((batch, d.num_attention_heads, s, d.head_dim), dtype=torch.bfloat16, device=dev),
-                "att": torch.empty((rows, H), dtype=torch.bfloat16, device=dev),
-                "act": torch.empty((rows, I), dtype=torch.bfloat16, device=dev),
-            }
-            if self.split:
-                for name in ("x16", "q", "att", "act"):
-                    ws[name + "_lo"] = torch.empty_like(ws[name])
-            else:
-                for name in ("x16", "q", "att", "act"):
-                    ws[name + "_lo"] = None
-            self._ws, self._ws_key = ws, key
+            self._ws, self._ws_key = self._alloc_workspace(batch, s), key
         return self._ws
+
+    def _alloc_workspace(self, batch: int, s: int):
+        d, dev = self.dims, self.device
+        rows = batch * s
+        H, I = d.hidden_size, d.intermediate_size
+        ws = {
+            "h": torch.empty((rows, H), dtype=torch.float32, device=dev),
+            "x16": torch.empty((rows, H), dtype=torch.bfloat16, device=dev),
+            "qkv": torch.empty((rows, 3 * H), dtype=torch.float32, device=dev),
+            "q": torch.empty((batch, d.num_attention_heads, s, d.head_dim), dtype=torch.bfloat16, device=dev),
+            "att": torch.empty((rows, H), dtype=torch.bfloat16, device=dev),
+            "act": torch.empty((rows, I), dtype=torch.bfloat16, device=dev),
+        }
+        if self.split:
+            for name in ("x16", "q", "att", "act"):
+                ws[name + "_lo"] = torch.empty_like(ws[name])
+        else:
+            for name in ("x16", "q", "att", "act"):
+                ws[name + "_lo"] = None
+        return ws
 
     def set_precision(self, precision: str) -> None:
         """Switch between the "split" (fp32-class) and "bf16" activation flows.  The weights are the same bf16 values in both;
@@ -282,6 +288,8 @@ class HipLlamaEngine:
         self._ws, self._ws_key = None, None
         self._dec.clear()
         self.k_cache = self.vt_cache = self.k_cache_lo = self.vt_cache_lo = None
+        self._slot_ws = None
+        self._clear_slots()
 
     def _ensure_cache(self, batch: int):
         d = self.dims
@@ -305,14 +313,19 @@ class HipLlamaEngine:
         return ops.gemm16_fragw_whole_tiles(self.split, ops.EPI_F32, batch * s, 3 * H, H)
 
     # ---- forward -------------------------------------------------------------------------------
-    def _layers_forward(self, ws, batch: int, s: int, pos0: int, num_layers: Optional[int] = None, pos_dev=None, hidden_sink=None) -> bool:
+    def _layers_forward(self, ws, batch: int, s: int, pos0: int, num_layers: Optional[int] = None, pos_dev=None, hidden_sink=None,
+                        slot0: int = 0, pos_rows=None) -> bool:
         """Runs the decoder layers on ws["h"].  Returns True when ws["x16"] already holds RMSNorm_final(h) (the fused
-        decode path normalises inside the producing GEMM), False when the caller still has to apply the final norm."""
+        decode path normalises inside the producing GEMM), False when the caller still has to apply the final norm.
+        slot0: first KV-cache slot of these batch rows (ragged mode); pos_rows: int32 [batch] device positions of a ragged
+        decode step (s = 1), one per slot."""
         d = self.dims
         H, I, nh, hd = d.hidden_size, d.intermediate_size, d.num_attention_heads, d.head_dim
         h = ws["h"]
         n_layers = d.num_hidden_layers if num_layers is None else num_layers
         sp = self.split
+        if slot0 < 0 or slot0 + batch > self.k_cache.shape[1]:
+            raise ValueError(f"KV-cache slots {slot0} .. {slot0 + batch - 1} outside the {self.k_cache.shape[1]} allocated")
         # decode (one token per sequence): o_proj / down_proj carry the FOLLOWING RMSNorm in their launch
         fused = s == 1 and batch <= 16 and n_layers > 0 and self.fuse_decode_norm and H <= 8192 and hidden_sink is None
         norm_a = (s == 1 and batch <= 16 and not fused and H % 32 == 0 and
@@ -324,19 +337,19 @@ class HipLlamaEngine:
             rope_fused = all(self._rope_weight(self.layers[i]) is not None for i in range(n_layers))
         if (self.prefill_streams == 2 and rope_fused and batch >= 2 and batch % 2 == 0 and self._prefill_rope_fused(batch // 2, s)
                 and hidden_sink is None and not torch.cuda.is_current_stream_capturing()):
-            self._prefill_two_streams(ws, batch, s, pos0, n_layers)
+            self._prefill_two_streams(ws, batch, s, pos0, n_layers, slot0)
             return False
         if (self.decode_chain and s == 1 and batch == 1 and norm_a and self.fuse_decode_rope and pos_dev is None and hidden_sink is None
-                and not fused and H <= 4096 and not torch.cuda.is_current_stream_capturing()):
+                and not fused and H <= 4096 and slot0 == 0 and pos_rows is None and not torch.cuda.is_current_stream_capturing()):
             self._decode_layers_chained(ws, pos0, n_layers)
             return False
         for i in range(n_layers):
             L = self.layers[i]
             if hidden_sink is not None:                       # HF output_hidden_states: the stream as it ENTERS every layer
                 hidden_sink.append(h.view(batch, s, H).clone())
-            kc, vc = self.k_cache[i, :batch], self.vt_cache[i, :batch]
-            kcl = self.k_cache_lo[i, :batch] if sp else None
-            vcl = self.vt_cache_lo[i, :batch] if sp else None
+            kc, vc = self.k_cache[i, slot0: slot0 + batch], self.vt_cache[i, slot0: slot0 + batch]
+            kcl = self.k_cache_lo[i, slot0: slot0 + batch] if sp else None
+            vcl = self.vt_cache_lo[i, slot0: slot0 + batch] if sp else None
             if not kc.is_contiguous():            # batch smaller than the allocated cache
                 raise ops._lib.LlarkHipError("KV cache batch mismatch: call reset(batch) before prefill")
             if rope_fused:                           # prefill: RoPE / head split / cache writes in the q|k|v epilogue
@@ -351,6 +364,8 @@ class HipLlamaEngine:
                 ops.gemm16(ws["x16"], ws["x16_lo"], L.wqkv, None, 3 * H, ops.EPI_F32, c=ws["qkv"])
             if rope_fused:
                 ops.attn_prefill(ws["q"], kc, vc, batch, s, nh, hd, pos0, ws["att"], ws["q_lo"], kcl, vcl, ws["att_lo"])
+            elif pos_rows is not None:               # ragged decode step: RoPE / cache append / attention at each slot's own position
+                ops.attn_decode_rope_rows(ws["qkv"], batch, nh, hd, pos_rows, self.cos, self.sin, kc, vc, ws["att"], kcl, vcl, ws["att_lo"])
             elif s == 1 and self.fuse_decode_rope:
                 ops.attn_decode_rope(ws["qkv"], batch, nh, hd, pos_dev if pos_dev is not None else pos0, self.cos, self.sin, kc, vc,
                                      ws["att"], kcl, vcl, ws["att_lo"])
@@ -423,8 +438,9 @@ class HipLlamaEngine:
             ops.gemm16(ws["act"], ws["act_lo"], L.wdown, None, H, ops.EPI_RESID, c=h, resid=h)
         main.wait_stream(side)                                   # (the data dependency is already met through O_i: this is for the allocator's sake)
 
-    def _prefill_layer_rows(self, ws, L, i: int, b0: int, b1: int, s: int, pos0: int) -> None:
-        """One decoder layer of a PREFILL on batch rows b0 .. b1 - 1 (the fused-RoPE path of _layers_forward on row slices)."""
+    def _prefill_layer_rows(self, ws, L, i: int, b0: int, b1: int, s: int, pos0: int, slot0: int = 0) -> None:
+        """One decoder layer of a PREFILL on batch rows b0 .. b1 - 1 (the fused-RoPE path of _layers_forward on row slices); their
+        KV-cache slots start at slot0 + b0."""
         d = self.dims
         H, I, nh, hd = d.hidden_size, d.intermediate_size, d.num_attention_heads, d.head_dim
         sp, nb = self.split, b1 - b0
@@ -435,9 +451,10 @@ class HipLlamaEngine:
         attl = ws["att_lo"][r0:r1] if sp else None
         actl = ws["act_lo"][r0:r1] if sp else None
         ql = ws["q_lo"][b0:b1] if sp else None
-        kc, vc = self.k_cache[i, b0:b1], self.vt_cache[i, b0:b1]
-        kcl = self.k_cache_lo[i, b0:b1] if sp else None
-        vcl = self.vt_cache_lo[i, b0:b1] if sp else None
+        c0, c1 = slot0 + b0, slot0 + b1
+        kc, vc = self.k_cache[i, c0:c1], self.vt_cache[i, c0:c1]
+        kcl = self.k_cache_lo[i, c0:c1] if sp else None
+        vcl = self.vt_cache_lo[i, c0:c1] if sp else None
         ops.rmsnorm_bf16(h, L.ln1, d.rms_norm_eps, x16, x16l)
         ops.gemm16_fragw_rope_qkv(x16, x16l, L.wqkv_rope, H, nb, s, nh, pos0, self.cos, self.sin, q, kc, vc, ql, kcl, vcl)
         ops.attn_prefill(q, kc, vc, nb, s, nh, hd, pos0, att, ql, kcl, vcl, attl)
@@ -446,7 +463,7 @@ class HipLlamaEngine:
         ops.gemm16(x16, x16l, L.wgu, None, 2 * I, ops.EPI_SWIGLU_SPLIT if sp else ops.EPI_SWIGLU16, out_hi=act, out_lo=actl)
         ops.gemm16(act, actl, L.wdown, None, H, ops.EPI_RESID, c=h, resid=h)
 
-    def _prefill_two_streams(self, ws, batch: int, s: int, pos0: int, n_layers: int) -> None:
+    def _prefill_two_streams(self, ws, batch: int, s: int, pos0: int, n_layers: int, slot0: int = 0) -> None:
         """The layer stack of a prefill as two half-batches, each on its own stream, enqueued layer by layer in alternation.
         The side streams work on row slices of `ws`, tensors allocated on the CALLER's stream: safe only because the workspace is
         persistent (owned by the engine, never returned to the caching allocator while a forward is in flight) and both side streams
@@ -462,7 +479,7 @@ class HipLlamaEngine:
             L = self.layers[i]
             for st, (b0, b1) in zip(self._side_streams, parts):
                 with torch.cuda.stream(st):
-                    self._prefill_layer_rows(ws, L, i, b0, b1, s, pos0)
+                    self._prefill_layer_rows(ws, L, i, b0, b1, s, pos0, slot0)
         for st in self._side_streams:
             cur.wait_stream(st)
 
@@ -535,6 +552,7 @@ class HipLlamaEngine:
             self.k_cache = self.vt_cache = self.k_cache_lo = self.vt_cache_lo = None
         self._ensure_cache(batch)
         self.cur_len, self.cur_batch = 0, batch
+        self._clear_slots()
 
     def forward_tokens(self, input_ids: torch.Tensor, audio_segments: Sequence[Tuple[int, int, torch.Tensor]] = (),
                        pos0: int = 0, last_only: bool = False, num_layers: Optional[int] = None,
@@ -591,3 +609,160 @@ class HipLlamaEngine:
             ops.rmsnorm_bf16(h, self.norm, d.rms_norm_eps, ws["x16"], ws["x16_lo"])
         ops.gemm16(ws["x16"], ws["x16_lo"], self.lm_head, None, d.vocab_size, ops.EPI_F32, c=logits)
         return logits.view(B, S, d.vocab_size)
+
+    # ---- ragged mode: batch slots with their own cache lengths ---------------------------------------------------------
+    # Next to the uniform forward_tokens / cur_len mode (which it leaves untouched): slot b of the KV cache holds one sequence of
+    # slot_len[b] tokens (-1 = idle).  prefill_slots fills slots with new prompts at position 0 while the other slots keep their
+    # state, decode_slots runs one token for every slot at its own position, release_slots frees slots for a refill.  The decode
+    # GEMMs are the m <= 16 forms, hence at most 16 slots.
+    def _clear_slots(self) -> None:
+        self.n_slots = 0
+        self.slot_len = self.slot_state = None                 # device int32 [n_slots]: positions, ops.ROW_* states
+        self.slot_len_host: List[int] = []
+        self.slot_state_host: List[int] = []
+
+    def init_slots(self, n_slots: int) -> None:
+        """Enter the ragged mode with `n_slots` idle slots (the KV cache is (re)sized to n_slots sequences)."""
+        if not 1 <= n_slots <= min(self.max_batch, 16):
+            raise ValueError(f"n_slots must be in 1 .. {min(self.max_batch, 16)} (max_batch {self.max_batch}, decode GEMMs m <= 16), got {n_slots}")
+        self.reset(n_slots)
+        self.n_slots = n_slots
+        self.slot_len = torch.full((n_slots,), -1, dtype=torch.int32, device=self.device)
+        self.slot_state = torch.full((n_slots,), ops.ROW_IDLE, dtype=torch.int32, device=self.device)
+        self.slot_len_host, self.slot_state_host = [-1] * n_slots, [ops.ROW_IDLE] * n_slots
+
+    def _check_slots(self, slots: Sequence[int]) -> List[int]:
+        if self.n_slots == 0:
+            raise RuntimeError("ragged mode is not active: call init_slots(n) first")
+        slots = [int(b) for b in slots]
+        if len(set(slots)) != len(slots) or any(not 0 <= b < self.n_slots for b in slots):
+            raise ValueError(f"slots must be distinct and in 0 .. {self.n_slots - 1}, got {slots}")
+        return slots
+
+    def _set_slots(self, slots: List[int], lens: List[int], state: int) -> None:
+        idx = torch.tensor(slots, dtype=torch.long, device=self.device)
+        self.slot_len[idx] = torch.tensor(lens, dtype=torch.int32, device=self.device)
+        self.slot_state[idx] = state
+        for b, n in zip(slots, lens):
+            self.slot_len_host[b], self.slot_state_host[b] = n, state
+
+    def release_slots(self, slots: Sequence[int]) -> None:
+        """Mark slots idle: the decode step leaves their caches alone and they emit the pad token."""
+        slots = self._check_slots(slots)
+        if slots:
+            self._set_slots(slots, [-1] * len(slots), ops.ROW_IDLE)
+
+    def prefill_slots(self, rows: Sequence[torch.Tensor], audio_segments: Sequence[Tuple[int, int, torch.Tensor]] = (),
+                      slots: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """Prefill new sequences into the given slots at position 0; the other slots keep their caches and positions.
+        rows: 1-D int64 token tensors (one per new sequence); audio_segments: (index into rows, position of <audio_start>, frames
+        fp32 (F, mm)) as in forward_tokens; slots: the slot of each row (default 0 .. len(rows) - 1).  A run of contiguous slots is
+        prefilled as ONE right-padded batch: causal attention never lets a valid position see a pad, and the cache rows written for
+        pad positions lie beyond the slot's length, where the decode step overwrites them before it reads them.
+        Returns fp32 logits [len(rows), V] of each row's LAST valid token; sets slot_len = row length, state active."""
+        d = self.dims
+        assert self.embed is not None and all(L is not None for L in self.layers), "weights not loaded"
+        slots = self._check_slots(range(len(rows)) if slots is None else slots)
+        if len(slots) != len(rows):
+            raise ValueError(f"{len(rows)} rows for {len(slots)} slots")
+        rows = [r.reshape(-1).to(device=self.device, dtype=torch.int64) for r in rows]
+        lens = [int(r.numel()) for r in rows]
+        if any(n < 1 or n > self.smax for n in lens):
+            raise ValueError(f"row lengths {lens} must be in 1 .. max_seq {self.smax}")
+        logits = torch.empty((len(rows), d.vocab_size), dtype=torch.float32, device=self.device)
+        order = sorted(range(len(rows)), key=lambda r: slots[r])
+        runs: List[List[int]] = []
+        for r in order:
+            if runs and slots[r] == slots[runs[-1][-1]] + 1:
+                runs[-1].append(r)
+            else:
+                runs.append([r])
+        for run in runs:
+            nb, S = len(run), max(lens[r] for r in run)
+            ids = torch.zeros((nb, S), dtype=torch.int64, device=self.device)
+            for i, r in enumerate(run):
+                ids[i, : lens[r]] = rows[r]
+            segs = [(i, start, frames) for i, r in enumerate(run) for (rr, start, frames) in audio_segments if rr == r]
+            last = torch.tensor([i * S + lens[r] - 1 for i, r in enumerate(run)], dtype=torch.long, device=self.device)
+            logits[torch.tensor(run, dtype=torch.long, device=self.device)] = self._prefill_run(ids, segs, slots[run[0]], last)
+        self._set_slots(slots, lens, ops.ROW_ACTIVE)
+        return logits
+
+    def _prefill_run(self, ids: torch.Tensor, segs, slot0: int, last: torch.Tensor) -> torch.Tensor:
+        """forward_tokens(last_only=True) of a right-padded batch into cache slots slot0 .., logits of the rows of h listed in `last`."""
+        d = self.dims
+        B, S = ids.shape
+        ws = self._workspace(B, S)
+        h = ws["h"]
+        ops.embed_gather(ids.reshape(-1), self.embed, h)
+        for (b, start, frames) in segs:
+            assert self.proj_w is not None, "mm_projector weights not loaded"
+            F = frames.shape[0]
+            a16, a16_lo = ops.split16(frames.to(device=self.device, dtype=torch.float32).contiguous(), torch.bfloat16, want_lo=self.split)
+            r0 = b * S + start + 1
+            ops.gemm16(a16, a16_lo, self.proj_w, self.proj_b, d.hidden_size, ops.EPI_F32, c=h[r0: r0 + F])
+        self._layers_forward(ws, B, S, 0, slot0=slot0)
+        hl = h.index_select(0, last)
+        x16 = torch.empty((B, d.hidden_size), dtype=torch.bfloat16, device=self.device)
+        x16_lo = torch.empty_like(x16) if self.split else None
+        ops.rmsnorm_bf16(hl, self.norm, d.rms_norm_eps, x16, x16_lo)
+        logits = torch.empty((B, d.vocab_size), dtype=torch.float32, device=self.device)
+        ops.gemm16(x16, x16_lo, self.lm_head, None, d.vocab_size, ops.EPI_F32, c=logits)
+        return logits
+
+    def _slot_workspace(self):
+        """The decode step's own buffers: a refill prefill (other shapes) does not reallocate them."""
+        n = self.n_slots
+        if self._slot_ws is None or self._slot_ws["h"].shape[0] != n:
+            ws = self._alloc_workspace(n, 1)
+            ws["logits"] = torch.empty((n, self.dims.vocab_size), dtype=torch.float32, device=self.device)
+            ws["next"] = torch.zeros((n,), dtype=torch.int64, device=self.device)
+            self._slot_ws = ws
+        return self._slot_ws
+
+    def advance_slots(self, logits: torch.Tensor, eos: int = -1, pad: int = 0, out_col: Optional[torch.Tensor] = None,
+                      choice: Optional[torch.Tensor] = None, advance: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Token choice of every active slot from fp32 logits [n_slots, V] (greedy, or `choice` [n_slots] int64), EOS -> finished,
+        pad for idle / finished slots, positions + 1 for active slots when `advance` (ops.decode_advance_rows, one launch).
+        Returns (next ids on the device [n_slots] int64, their host copy -- the step's one device-to-host transfer)."""
+        ws = self._slot_workspace()
+        was_active = [st == ops.ROW_ACTIVE for st in self.slot_state_host]
+        ops.decode_advance_rows(logits, self.slot_state, ws["next"], self.slot_len if advance else None, out_col, eos, pad,
+                                choice=None if choice is None else choice.reshape(-1).to(torch.int64).contiguous())
+        host = ws["next"].cpu()
+        for b, act in enumerate(was_active):
+            if act:
+                if advance:
+                    self.slot_len_host[b] += 1
+                if eos >= 0 and int(host[b]) == eos:
+                    self.slot_state_host[b] = ops.ROW_FINISHED
+        return ws["next"], host
+
+    def decode_slots(self, ids: torch.Tensor, eos: int = -1, pad: int = 0, out_col: Optional[torch.Tensor] = None,
+                     sample=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """One decode step over all n_slots rows, each at its own position: embedding -> decoder layers (the uniform decode GEMMs;
+        attention by ops.attn_decode_rope_rows over slot_len) -> final norm + lm_head -> advance_slots.  ids: int64 [n_slots] (the
+        token of each slot at position slot_len; idle rows pass through the row-independent GEMMs harmlessly).  sample: optional
+        callable logits -> int64 [n_slots] tokens (sampling); greedy otherwise.  Returns (next ids on the device, their host copy,
+        the step's fp32 logits [n_slots, V] -- a buffer the next step overwrites)."""
+        d = self.dims
+        n = self.n_slots
+        if n == 0:
+            raise RuntimeError("ragged mode is not active: call init_slots(n) first")
+        full = [b for b in range(n) if self.slot_state_host[b] == ops.ROW_ACTIVE and self.slot_len_host[b] >= self.smax]
+        if full:
+            raise ValueError(f"slot(s) {full} reached the engine's max_seq {self.smax}")
+        ids = ids.reshape(-1)
+        assert ids.numel() == n and ids.dtype == torch.int64
+        ws = self._slot_workspace()
+        h, logits = ws["h"], ws["logits"]
+        ops.embed_gather(ids.contiguous(), self.embed, h)
+        normed = self._layers_forward(ws, n, 1, 0, pos_rows=self.slot_len)
+        if not normed and (self.fuse_decode_norm_a == "1" or (self.fuse_decode_norm_a == "auto" and ops.gemv_dma_rmsnorm_takes(n, d.vocab_size, d.hidden_size))):
+            ops.gemm16_rmsnorm_a(h, self.norm, d.rms_norm_eps, self.lm_head, d.vocab_size, ops.EPI_F32, self.split, c=logits)
+        else:
+            if not normed:
+                ops.rmsnorm_bf16(h, self.norm, d.rms_norm_eps, ws["x16"], ws["x16_lo"])
+            ops.gemm16(ws["x16"], ws["x16_lo"], self.lm_head, None, d.vocab_size, ops.EPI_F32, c=logits)
+        nxt, host = self.advance_slots(logits, eos, pad, out_col, None if sample is None else sample(logits))
+        return nxt, host, logits

@@ -7,7 +7,10 @@ Here the same contract is served in batches on the HIP engine:
 
 * :func:`infer_from_encodings` -- same inputs / same CSV, ``batch_size`` examples per ``generate`` call;
 * :func:`infer_from_audio`     -- audio clips -> ``WrappedAudioEncoder`` -> LLM in ONE process: the ``(B, frames, 4800)``
-  embeddings never leave HBM (no ``.npy`` round trip).
+  embeddings never leave HBM (no ``.npy`` round trip);
+* :func:`infer_from_shards`    -- the contract of ``scripts/inference/infer_from_webdataset.py:51-151`` (local tar shards, one
+  example per question, per-example prompts) through :func:`generate_inflight`: ragged prompts share the engine's batch slots
+  and a finished row's slot is refilled with the next example while the other slots keep decoding.
 
 Batched greedy decoding is token-for-token the per-example loop of the reference: every kernel on the path is
 row-independent and accumulates each output element in the same k order whatever the batch size, and stopping is
@@ -17,7 +20,8 @@ from __future__ import annotations
 
 import glob
 import os
-from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple
+import random
+from typing import Any, Dict, Iterable, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -78,6 +82,141 @@ def generate_batch(model, input_ids: torch.Tensor, encodings: torch.Tensor, toke
                          eos_token_id=-1)                  # EOS is handled per row above
     out = out.cpu()
     return [out[b, : (done_at[b] if done_at[b] is not None else out.shape[1])] for b in range(B)]
+
+
+class InflightScheduler:
+    """Slot table of :func:`generate_inflight`, free of any GPU code so that it can run against a fake backend.
+
+    ``backend`` is the narrow model interface:
+      * ``prefill(slots, prompts, encodings) -> first tokens``: new examples (1-D int64 prompt ids, encoding or None) into the
+        given slots; returns the greedy token after each prompt, in the order of ``slots``;
+      * ``decode() -> tokens``: one decode step of every slot; returns a token per slot (entries of free slots are ignored);
+      * ``release(slots)``: the slots' examples are done.
+    Free slots are refilled in ascending slot order with examples in input order; a row stops on a keyword (``stop_fn``), on
+    ``eos`` or at its budget, exactly as :func:`generate_batch` decides per row.  ``trace`` records ``("prefill", slots, indices)``
+    and ``("done", slot, index)`` events."""
+
+    def __init__(self, backend, n_slots: int, max_new_tokens: int = 512, eos: Optional[int] = None, stop_fn=None):
+        if n_slots < 1:
+            raise ValueError(f"n_slots must be >= 1, got {n_slots}")
+        self.backend, self.n_slots, self.max_new_tokens = backend, n_slots, max_new_tokens
+        self.eos = eos if eos is not None and eos >= 0 else None
+        self.stop_fn = stop_fn                    # (prompt ids, generated ids) -> bool: keyword stop; may keep state per row
+        self.trace: List[Tuple] = []
+
+    def run(self, examples: Iterable[Sequence[Any]]) -> Iterator[Tuple[int, torch.Tensor]]:
+        """examples: (prompt_ids, encoding[, max_new_tokens]).  Yields (input index, prompt + generated ids) as rows finish; rows
+        finishing in the same step come out in input order."""
+        it = enumerate(examples)
+        exhausted = False
+        table: List[Optional[Dict[str, Any]]] = [None] * self.n_slots
+        while True:
+            free = [b for b in range(self.n_slots) if table[b] is None]
+            new: List[int] = []
+            while free and not exhausted:
+                try:
+                    idx, ex = next(it)
+                except StopIteration:
+                    exhausted = True
+                    break
+                prompt = torch.as_tensor(ex[0], dtype=torch.int64).reshape(-1).cpu()
+                budget = int(ex[2]) if len(ex) > 2 and ex[2] is not None else self.max_new_tokens
+                b = free.pop(0)
+                table[b] = {"index": idx, "prompt": prompt, "enc": ex[1], "budget": budget, "out": [], "stop": None}
+                new.append(b)
+            if new:
+                self.trace.append(("prefill", tuple(new), tuple(table[b]["index"] for b in new)))
+                firsts = self.backend.prefill(new, [table[b]["prompt"] for b in new], [table[b]["enc"] for b in new])
+                done = self._take(table, dict(zip(new, firsts)))
+                yield from done
+                if done and not exhausted:
+                    continue                       # refill the slots that finished at once before the next decode step
+            if all(r is None for r in table):
+                if exhausted:
+                    return
+                continue
+            toks = self.backend.decode()
+            yield from self._take(table, {b: toks[b] for b in range(self.n_slots) if table[b] is not None})
+
+    def _take(self, table, toks: Dict[int, int]) -> List[Tuple[int, torch.Tensor]]:
+        finished = []
+        for b in sorted(toks):
+            row = table[b]
+            t = int(toks[b])
+            row["out"].append(t)
+            if (len(row["out"]) >= row["budget"] or (self.eos is not None and t == self.eos)
+                    or (self.stop_fn is not None and self.stop_fn(row, torch.tensor(row["out"], dtype=torch.int64)))):
+                finished.append(b)
+        if not finished:
+            return []
+        self.backend.release(finished)
+        outs = []
+        for b in finished:
+            row = table[b]
+            table[b] = None
+            self.trace.append(("done", b, row["index"]))
+            outs.append((row["index"], torch.cat((row["prompt"], torch.tensor(row["out"], dtype=torch.int64)))))
+        return sorted(outs, key=lambda o: o[0])
+
+
+class EngineSlots:
+    """:class:`InflightScheduler` backend on the HIP engine's ragged slot mode (``HipLlamaEngine.init_slots`` /
+    ``prefill_slots`` / ``decode_slots`` / ``release_slots``) of a ``WrappedLlamav2ForCausalLM``."""
+
+    def __init__(self, model, n_slots: int):
+        from .llamav2 import plan_audio_splice
+
+        self._plan = plan_audio_splice
+        self.model = model
+        self.eng = model.engine
+        self.eng.init_slots(n_slots)
+        self.ids = torch.zeros((n_slots,), dtype=torch.int64, device=self.eng.device)
+
+    def prefill(self, slots, prompts, encodings):
+        eng = self.eng
+        cfg = self.model.get_model().audio_encoder_config
+        segs = []
+        for i, (p, enc) in enumerate(zip(prompts, encodings)):
+            if enc is not None:
+                feats = torch.as_tensor(enc).to(device=eng.device, dtype=torch.float32)
+                segs += [(i, start, f) for (_, start, f) in self._plan(p[None], [feats], cfg, False)]
+        logits = eng.prefill_slots([p.to(eng.device) for p in prompts], segs, slots)
+        first = logits.argmax(-1)                                  # what generate() picks after the prompt
+        self.ids[torch.tensor(slots, dtype=torch.long, device=eng.device)] = first
+        return first.cpu().tolist()
+
+    def decode(self):
+        self.ids, host, _ = self.eng.decode_slots(self.ids)
+        return host.tolist()
+
+    def release(self, slots):
+        self.eng.release_slots(slots)
+
+
+@torch.no_grad()
+def generate_inflight(model, examples: Iterable[Sequence[Any]], slots: int = 8, max_new_tokens: int = 512,
+                      keywords: Sequence[str] = ("###",), tokenizer=None, trace: Optional[list] = None) -> Iterator[Tuple[int, torch.Tensor]]:
+    """Greedy generation with in-flight slot refill.  ``examples`` yields ``(prompt_ids, encoding[, max_new_tokens])`` with prompts
+    of any length; up to ``slots`` of them decode together, each at its own KV-cache length, and a finished row's slot is refilled
+    from the iterable (contiguous free slots prefilled as one batch) while the others keep decoding.  Stops per row as in
+    :func:`generate_batch` (keyword -- needs ``tokenizer`` --, EOS or budget).  Yields ``(index, prompt + continuation ids)`` as
+    examples complete.  ``model`` may provide ``slot_backend(n_slots)`` (any :class:`InflightScheduler` backend); otherwise its
+    engine's ragged slot mode serves it.  ``trace``: a list that receives the scheduler's events."""
+    if keywords and tokenizer is None:
+        raise ValueError("generate_inflight: keyword stopping needs the tokenizer")
+    make = getattr(model, "slot_backend", None)
+    backend = make(slots) if make is not None else EngineSlots(model, slots)
+    eos = getattr(getattr(model, "generation_config", None), "eos_token_id", None)
+    stop_fn = None
+    if keywords:
+        def stop_fn(row, gen):
+            if row["stop"] is None:
+                row["stop"] = KeywordsStoppingCriteria(keywords=list(keywords), tokenizer=tokenizer, input_ids=row["prompt"][None])
+            return bool(row["stop"](torch.cat((row["prompt"], gen))[None], None))
+    sched = InflightScheduler(backend, slots, max_new_tokens, eos, stop_fn)
+    if trace is not None:
+        sched.trace = trace
+    yield from sched.run(examples)
 
 
 def _rows_to_records(example_ids, prompt, outs, end_seq, tokenizer) -> List[Dict[str, str]]:
@@ -182,6 +321,54 @@ def infer_from_audio(encoder, model, tokenizer, clips: Iterable[Tuple[str, np.nd
     return records
 
 
+SHARD_COLUMNS = ["example_id", "prompt_text", "original_completion_text", "model_completion_text"]
+
+
+def infer_from_shards(model, tokenizer, shards: str, multimodal_cfg: Dict[str, Any], end_seq: Sequence[int], outfile: Optional[str] = None,
+                      slots: int = 8, max_samples: Optional[int] = None, max_new_tokens: int = 512, prompt: Optional[str] = None,
+                      seed: int = 0, allow_pickle: bool = False, header: str = DEFAULT_CONVERSATION_HEADER) -> List[Dict[str, str]]:
+    """Local tar shards -> CSV under the contract of ``scripts/inference/infer_from_webdataset.py:51-151``: every (question,
+    answer) pair of a sample is one example whose prompt is its own human turn up to "### Assistant:" (audio placeholder first
+    or last by a draw seeded with ``seed``); ``prompt`` overrides every question (the reference's ``--prompt``: audio first).
+    Records ``example_id`` (the sample's tar key, repeated across its questions), ``prompt_text``, ``original_completion_text``
+    (the pair's answer) and ``model_completion_text``, in input order.  ``max_samples`` caps the number of examples.  All
+    generation runs through :func:`generate_inflight` with ``slots`` batch slots."""
+    from .data import element_to_conversations, expand_urls, iter_tar_samples
+
+    rng = random.Random(seed)
+    meta: List[Dict[str, str]] = []
+
+    def examples():
+        for elem in iter_tar_samples(expand_urls(shards), allow_pickle):
+            for conv in element_to_conversations(elem, rng):
+                if max_samples and len(meta) >= max_samples:
+                    return
+                ex = preprocess_for_lm_mappable(preprocess_multimodal_mappable(conv, multimodal_cfg), tokenizer=tokenizer, header=header)
+                enc = ex["audio_encoding"].float()
+                if prompt is None:
+                    ids = extract_prompt_tokens(ex["input_ids"], end_seq)
+                    prompt_text = tokenizer.decode(ids)
+                else:
+                    ids = build_prompt_ids(prompt, enc.shape[0], tokenizer, multimodal_cfg, end_seq, True, header)
+                    prompt_text = prompt
+                meta.append({"example_id": conv["id"], "prompt_text": prompt_text,
+                             "original_completion_text": tokenizer.decode(extract_response_tokens(ex["input_ids"], end_seq))})
+                yield ids, enc
+
+    outs: Dict[int, torch.Tensor] = dict(generate_inflight(model, examples(), slots=slots, max_new_tokens=max_new_tokens, tokenizer=tokenizer))
+    records = []
+    for i, m in enumerate(meta):
+        records.append(dict(m, model_completion_text=tokenizer.decode(extract_response_tokens(outs[i], end_seq))))
+    if outfile:
+        import pandas as pd
+
+        d = os.path.dirname(outfile)
+        if d and not os.path.exists(d):
+            os.makedirs(d)
+        pd.DataFrame(records, columns=SHARD_COLUMNS).to_csv(outfile, index=False)
+    return records
+
+
 def get_prompt_end_token_sequence(tokenizer, model_name: str, prompt_end_string: str = "\n### Assistant:") -> List[int]:
     """m2t/tokenizer.py:33-52: the token ids that mark the end of the prompt; the Llama-2 SentencePiece tokenizer prepends a
     piece to a string that starts with a newline, which is dropped."""
@@ -197,11 +384,6 @@ def main(argv=None):
         --outfile results/infer.csv [--max-samples N] [--max_new_tokens 512] [--batch-size 8] [--mm_hidden_size 4800]"""
     import argparse
 
-    from transformers import AutoTokenizer
-
-    from .llamav2 import WrappedLlamav2ForCausalLM
-    from .special_tokens import DEFAULT_AUDIO_END_TOKEN, DEFAULT_AUDIO_PATCH_TOKEN, DEFAULT_AUDIO_START_TOKEN
-
     ap = argparse.ArgumentParser(description="LLark inference over a directory of audio encodings on the HIP engine")
     ap.add_argument("--model_name_or_path", required=True)
     ap.add_argument("--audio-encodings-dir", required=True)
@@ -216,6 +398,20 @@ def main(argv=None):
     for ignored in ("--ckpt-num", "--report_to", "--bf16", "--tf32", "--output_dir"):
         ap.add_argument(ignored, default=None, help="accepted for script compatibility")
     args = ap.parse_args(argv)
+    model, tok, end_seq, mm_cfg = _load_for_inference(args, args.batch_size)
+    recs = infer_from_encodings(model, tok, args.audio_encodings_dir, args.prompt, mm_cfg, end_seq, outfile=args.outfile,
+                                batch_size=args.batch_size, max_samples=args.max_samples, max_new_tokens=args.max_new_tokens)
+    print(f"writing {len(recs)} results to {args.outfile}")
+    return recs
+
+
+def _load_for_inference(args, max_batch: int):
+    """Tokenizer + model of ``args.model_name_or_path`` set up for generation (audio tokens, engine) -> (model, tokenizer, end_seq,
+    multimodal config)."""
+    from transformers import AutoTokenizer
+
+    from .llamav2 import WrappedLlamav2ForCausalLM
+    from .special_tokens import DEFAULT_AUDIO_END_TOKEN, DEFAULT_AUDIO_PATCH_TOKEN, DEFAULT_AUDIO_START_TOKEN
 
     tok = AutoTokenizer.from_pretrained(args.model_name_or_path, model_max_length=args.model_max_length, padding_side="right", use_fast=False)
     model = WrappedLlamav2ForCausalLM.from_pretrained(args.model_name_or_path, torch_dtype=torch.bfloat16)
@@ -235,14 +431,47 @@ def main(argv=None):
     else:
         model.initialize_audio_tokenizer(mm_use_audio_start_end=True, tokenizer=tok, device="cpu")
     model.cuda().eval()
-    model.configure_engine(max_batch=args.batch_size, max_seq=args.model_max_length, precision=args.llm_precision)
+    model.configure_engine(max_batch=max_batch, max_seq=args.model_max_length, precision=args.llm_precision)
     end_seq = get_prompt_end_token_sequence(tok, args.model_name_or_path)
     mm_cfg = dict(is_multimodal=True, sep_audio_conv_front=False, use_audio_start_end=True)
-    recs = infer_from_encodings(model, tok, args.audio_encodings_dir, args.prompt, mm_cfg, end_seq, outfile=args.outfile,
-                                batch_size=args.batch_size, max_samples=args.max_samples, max_new_tokens=args.max_new_tokens)
+    return model, tok, end_seq, mm_cfg
+
+
+def main_shards(argv=None):
+    """``shards`` mode, with the flags of the reference's ``scripts/inference/infer_from_webdataset.py:154-190`` (+ ``--slots``):
+    python -m llark_amd.m2t.infer_driver shards --model_name_or_path <dir> --eval_data_path "shards-{000000..000021}.tar" \
+        --outfile results/infer.csv [--prompt "Describe ..."] [--max-samples N] [--max_new_tokens 2048] [--slots 8] [--allow-pickle]
+    ``--allow-pickle``: read ``.pyd`` (pickled) encodings -- unpickling runs code, pass it only for shards you trust."""
+    import argparse
+
+    ap = argparse.ArgumentParser(description="LLark inference over local webdataset shards on the HIP engine (in-flight batching)")
+    ap.add_argument("--model_name_or_path", required=True)
+    ap.add_argument("--eval_data_path", required=True)
+    ap.add_argument("--prompt", default=None)
+    ap.add_argument("--outfile", default="infer_results.csv")
+    ap.add_argument("--max-samples", type=int, default=None)
+    ap.add_argument("--max_new_tokens", type=int, default=2048)
+    ap.add_argument("--slots", type=int, default=8)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--allow-pickle", action="store_true")
+    ap.add_argument("--mm_hidden_size", type=int, default=None)
+    ap.add_argument("--model_max_length", type=int, default=2048)
+    ap.add_argument("--llm-precision", default="split", choices=["split", "bf16"])
+    for ignored in ("--ckpt-num", "--report_to", "--bf16", "--tf32", "--output_dir"):
+        ap.add_argument(ignored, default=None, help="accepted for script compatibility")
+    args = ap.parse_args(argv)
+    model, tok, end_seq, mm_cfg = _load_for_inference(args, args.slots)
+    recs = infer_from_shards(model, tok, args.eval_data_path, mm_cfg, end_seq, outfile=args.outfile, slots=args.slots,
+                             max_samples=args.max_samples, max_new_tokens=args.max_new_tokens, prompt=args.prompt, seed=args.seed,
+                             allow_pickle=args.allow_pickle)
     print(f"writing {len(recs)} results to {args.outfile}")
     return recs
 
 
 if __name__ == "__main__":
-    main()
+    import sys
+
+    if len(sys.argv) > 1 and sys.argv[1] == "shards":
+        main_shards(sys.argv[2:])
+    else:
+        main()

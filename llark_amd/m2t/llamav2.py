@@ -336,11 +336,16 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
 
     @torch.no_grad()
     def generate(self, input_ids=None, audio_encodings=None, max_new_tokens: int = 20, do_sample: bool = False,
-                 stopping_criteria=None, eos_token_id=None, temperature: float = 1.0, **kwargs):
+                 stopping_criteria=None, eos_token_id=None, temperature: float = 1.0, attention_mask=None, **kwargs):
         """Greedy / temperature sampling loop with the semantics of HF 4.29.2 ``generate`` driven by
         :meth:`prepare_inputs_for_generation`: the full prompt (with audio) once, then one token per step
         against the engine's KV cache; ``stopping_criteria`` are called as ``c(ids, scores)`` each step
-        (m2t/generate.py:31-44, m2t/infer.py:146-152)."""
+        (m2t/generate.py:31-44, m2t/infer.py:146-152).  An ``attention_mask`` with zeros (left-padded, the HF convention for
+        batched decoder-only generation, or right-padded) runs every row as if it were alone on the engine's ragged slot mode
+        (:meth:`_generate_ragged`); ``None`` or all ones takes this uniform path."""
+        if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
+            return self._generate_ragged(input_ids, attention_mask, audio_encodings, max_new_tokens, do_sample, stopping_criteria,
+                                         eos_token_id, temperature)
         ids = input_ids.to(self.engine.device)
         eos = eos_token_id if eos_token_id is not None else getattr(self.generation_config, "eos_token_id", None)
         pad = getattr(self.generation_config, "pad_token_id", None)
@@ -379,6 +384,62 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
             if stopping_criteria is not None and any(bool(c(ids, scores)) for c in stopping_criteria):
                 break
         return ids
+
+    def _generate_ragged(self, input_ids, attention_mask, audio_encodings, max_new_tokens, do_sample, stopping_criteria, eos_token_id,
+                         temperature):
+        """generate() over a padded batch: row b is the sequence input_ids[b][mask[b]] at positions 0 .. len_b - 1 (HF's
+        position_ids = cumsum(mask) - 1), one engine slot per row (prefill_slots / decode_slots).  Returns the HF layout: the input
+        as given followed by the new tokens; rows that finished emit the pad token."""
+        eng = self.engine
+        B, S = input_ids.shape
+        am = attention_mask.to(device="cpu", dtype=torch.bool)
+        if am.shape != (B, S):
+            raise ValueError(f"attention_mask shape {tuple(am.shape)} does not match input_ids {(B, S)}")
+        lens = am.sum(1)
+        if bool((lens == 0).any()):
+            raise ValueError("attention_mask selects no token in some row")
+        ids_dev = input_ids.to(eng.device)
+        if max_new_tokens <= 0:
+            return ids_dev
+        ids_cpu = input_ids.detach().cpu()
+        rows = [ids_cpu[b][am[b]] for b in range(B)]
+        packed = torch.zeros((B, int(lens.max())), dtype=torch.int64)               # right-aligned copy for the splice plan
+        for b, r in enumerate(rows):
+            packed[b, : r.numel()] = r
+        segs = []
+        if audio_encodings is not None:
+            feats = audio_encodings
+            if isinstance(feats, (list, tuple)):
+                feats = [f.to(device=eng.device, dtype=torch.float32) for f in feats]
+            else:
+                feats = feats.to(device=eng.device, dtype=torch.float32)
+            segs = plan_audio_splice(packed, feats, self.model.audio_encoder_config, False)
+        eos = eos_token_id if eos_token_id is not None else getattr(self.generation_config, "eos_token_id", None)
+        pad = getattr(self.generation_config, "pad_token_id", None)
+        pad = eos if pad is None else pad
+        use_eos = eos is not None and eos >= 0
+        eos_k, pad_k = (int(eos), int(pad)) if use_eos else (-1, 0)
+
+        def sample(scores):
+            return torch.multinomial(torch.softmax(scores / max(temperature, 1e-6), dim=-1), 1).view(-1)
+
+        out = torch.empty((B, S + max_new_tokens), dtype=torch.int64, device=eng.device)
+        out[:, :S] = ids_dev
+        eng.init_slots(B)
+        scores = eng.prefill_slots([r.to(eng.device) for r in rows], segs, range(B))
+        nxt, _ = eng.advance_slots(scores, eos_k, pad_k, out[:, S], sample(scores) if do_sample else None, advance=False)
+        n = 1
+        while True:
+            cur = out[:, : S + n]
+            if use_eos and all(st != ops.ROW_ACTIVE for st in eng.slot_state_host):
+                break
+            if stopping_criteria is not None and any(bool(c(cur, scores)) for c in stopping_criteria):
+                break
+            if n == max_new_tokens:
+                break
+            nxt, _, scores = eng.decode_slots(nxt, eos_k, pad_k, out[:, S + n], sample if do_sample else None)
+            n += 1
+        return out[:, : S + n]
 
     def initialize_audio_tokenizer(self, mm_use_audio_start_end, tokenizer, device, tune_mm_mlp_adapter=False,
                                    pretrain_mm_mlp_adapter=None):

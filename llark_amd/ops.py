@@ -895,6 +895,60 @@ def attn_decode_rope(qkv: torch.Tensor, batch: int, nh: int, hd: int, pos, cos_t
                                                  _opt(alibi_slopes, "alibi_slopes", torch.float32), _stream()), "attn_decode_rope")
 
 
+ROW_IDLE, ROW_ACTIVE, ROW_FINISHED = 0, 1, 2          # LLARK_ROW_* of include/llark_hip.h (decode_advance_rows states)
+
+
+def attn_decode_rope_rows(qkv: torch.Tensor, batch: int, nh: int, hd: int, pos_rows: torch.Tensor, cos_t, sin_t, k_cache, vt_cache, out,
+                          k_cache_lo=None, vt_cache_lo=None, out_lo=None, alibi_slopes=None) -> None:
+    """:func:`attn_decode_rope` with one position per sequence: ``pos_rows`` int32 [batch] on the device (< 0 = idle slot: its caches
+    stay untouched and its output head is zero).  Ragged decode over batch slots."""
+    smax = k_cache.shape[-2]
+    bf = torch.bfloat16
+    assert qkv.shape == (batch, 3 * nh * hd) and pos_rows.numel() == batch and out.numel() == batch * nh * hd
+    assert k_cache.shape == (batch, nh, smax, hd) and vt_cache.shape == (batch, nh, hd, smax) and cos_t.shape == sin_t.shape
+    assert out_lo is None or out_lo.shape == out.shape
+    for c in (k_cache_lo, vt_cache_lo):
+        assert c is None or c.shape in (k_cache.shape, vt_cache.shape)
+    assert alibi_slopes is None or alibi_slopes.numel() >= nh
+    check(_lib.lib().llark_attn_decode_rope_bf16_rows(_dev(qkv, "qkv", torch.float32), batch, nh, hd, _dev(pos_rows, "pos_rows", torch.int32),
+                                                      _dev(cos_t, "cos", torch.float32), _dev(sin_t, "sin", torch.float32), cos_t.shape[0],
+                                                      _dev(k_cache, "k_cache", bf), _dev(vt_cache, "vt_cache", bf),
+                                                      _opt(k_cache_lo, "k_cache_lo", bf), _opt(vt_cache_lo, "vt_cache_lo", bf), smax,
+                                                      _dev(out, "out", bf), _opt(out_lo, "out_lo", bf),
+                                                      _opt(alibi_slopes, "alibi_slopes", torch.float32), _stream()), "attn_decode_rope_rows")
+
+
+def decode_advance_rows(logits: Optional[torch.Tensor], state: torch.Tensor, next_ids: torch.Tensor, pos_rows: Optional[torch.Tensor] = None,
+                        out_col: Optional[torch.Tensor] = None, eos: int = -1, pad: int = 0, choice: Optional[torch.Tensor] = None,
+                        vocab: Optional[int] = None) -> None:
+    """Bookkeeping of one ragged decode step in one launch: for every ROW_ACTIVE row the greedy token (torch.argmax of
+    ``logits[b, :vocab]``, or ``choice[b]``) goes to ``next_ids[b]`` and ``out_col[b]``, ``eos`` turns the row ROW_FINISHED and
+    ``pos_rows[b]`` advances by one; idle / finished rows emit ``pad``.  ``out_col``: an int64 column view, e.g. ``ids[:, t]``."""
+    batch = state.numel()
+    i64 = torch.int64
+    assert next_ids.numel() == batch and (pos_rows is None or pos_rows.numel() == batch)
+    assert logits is not None or choice is not None
+    ldl = 0
+    if logits is not None:
+        assert logits.dim() == 2 and logits.shape[0] == batch and logits.stride(1) == 1
+        vocab = logits.shape[1] if vocab is None else vocab
+        assert 0 < vocab <= logits.shape[1]
+        ldl = logits.stride(0)
+    if choice is not None:
+        assert choice.numel() == batch
+        vocab = vocab or 1
+    ld_out = 1
+    if out_col is not None:
+        assert out_col.dim() == 1 and out_col.shape[0] == batch and out_col.dtype == i64 and out_col.is_cuda
+        ld_out = out_col.stride(0)
+    check(_lib.lib().llark_decode_advance_rows(_dev(logits, "logits", torch.float32, contiguous=False) if logits is not None else None, ldl,
+                                               int(vocab), batch, _opt(choice, "choice", i64),
+                                               _opt(pos_rows, "pos_rows", torch.int32), _dev(state, "state", torch.int32),
+                                               _dev(next_ids, "next_ids", i64),
+                                               _dev(out_col, "out_col", i64, contiguous=False) if out_col is not None else None, ld_out,
+                                               int(eos), int(pad), _stream()), "decode_advance_rows")
+
+
 # ------------------------------------------------------------------------------------------------
 # MPT
 # ------------------------------------------------------------------------------------------------

@@ -1,0 +1,181 @@
+#!/usr/bin/env python3
+"""Generation throughput on a ragged workload: per-example batch-1 generate vs the grouped generate_batch vs in-flight slot refill.
+
+Llama-2-7B dimensions with random weights (no checkpoint offline), 64 synthetic examples: 240 audio frames (about 1 in 4 a shorter
+clip of 121 frames), prompt texts of 8-80 tokens, seeded per-example answer budgets of 16-256 tokens (random weights never emit
+"###", so the budget is what makes answer lengths vary; keyword and EOS stops are off).  Schedules:
+  (a) batch1   -- model.generate per example;
+  (b) grouped  -- generate_batch over groups of up to 8 examples sharing one prompt length (what the uniform engine allows), each
+                  group decoding until its longest budget, rows cut at their own budget;
+  (c) inflight -- generate_inflight with 8 and with 16 slots.
+Also the decode-step time of the ragged step with every slot active (1, 8, 16 slots).  Prints ONE JSON line.
+
+    python scripts/bench_generate_inflight.py [--examples 64] [--precision split] [--seed 0]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+import types
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from llark_amd.m2t import bench_support as BS  # noqa: E402
+from llark_amd.m2t.engine import HipLlamaEngine, LlamaDims  # noqa: E402
+from llark_amd.m2t.infer_driver import generate_batch, generate_inflight  # noqa: E402
+from llark_amd.m2t.llamav2 import WrappedLlamav2ForCausalLM  # noqa: E402
+
+
+class _NoText:
+    """generate_batch builds a keyword criterion per row; with no keywords it only needs batch_decode."""
+
+    def __call__(self, text, **kw):
+        return types.SimpleNamespace(input_ids=[0, 0])
+
+    def batch_decode(self, rows, skip_special_tokens=False):
+        return [""] * len(rows)
+
+
+class RandomLlama:
+    """The generate surface of WrappedLlamav2ForCausalLM (its own generate / ragged generate code) over a HipLlamaEngine with random
+    Llama-2-7B weights: building the HF module at 7B on the host would take minutes and ~27 GB for weights that are random anyway."""
+
+    generate = WrappedLlamav2ForCausalLM.generate
+    _generate_ragged = WrappedLlamav2ForCausalLM._generate_ragged
+    prepare_inputs_for_generation = WrappedLlamav2ForCausalLM.prepare_inputs_for_generation
+
+    def __init__(self, precision: str, max_batch: int, max_seq: int):
+        dims = LlamaDims(vocab_size=BS.VOCAB)
+        eng = HipLlamaEngine(dims, "cuda", max_batch=max_batch, max_seq=max_seq, precision=precision)
+        g = torch.Generator(device="cuda").manual_seed(0)
+        H, I = dims.hidden_size, dims.intermediate_size
+
+        def n(*shape):
+            return (torch.randn(*shape, generator=g, device="cuda", dtype=torch.float32) * 0.02).to(torch.bfloat16)
+
+        ones = torch.ones(H, device="cuda")
+        for i in range(dims.num_hidden_layers):
+            eng.set_layer(i, n(H, H), n(H, H), n(H, H), n(H, H), n(I, H), n(I, H), n(H, I), ones, ones)
+        eng.set_globals(n(BS.VOCAB, H), ones, n(BS.VOCAB, H), n(H, dims.mm_hidden_size), torch.zeros(H, device="cuda"))
+        eng.prepare_prefill()
+        self.engine = eng
+        self.generation_config = types.SimpleNamespace(eos_token_id=None, pad_token_id=None)
+        ac = types.SimpleNamespace(use_audio_start_end=True, audio_start_token=BS.START, audio_end_token=BS.END, audio_patch_token=BS.PATCH)
+        self.model = types.SimpleNamespace(audio_encoder_config=ac)
+
+    def get_model(self):
+        return self.model
+
+
+def make_examples(n: int, seed: int):
+    g = torch.Generator().manual_seed(seed)
+    out = []
+    for i in range(n):
+        frames = 121 if int(torch.randint(0, 4, (1,), generator=g)) == 0 else 240
+        text = int(torch.randint(8, 81, (1,), generator=g))
+        budget = int(torch.randint(16, 257, (1,), generator=g))
+        ids = torch.tensor([1, BS.START] + [BS.PATCH] * frames + [BS.END] + torch.randint(3, 32000, (text,), generator=g).tolist())
+        enc = torch.randn(frames, 4800, generator=g)
+        out.append((ids, enc, budget))
+    return out
+
+
+def run_batch1(model, examples, tok):
+    outs = {}
+    for i, (ids, enc, budget) in enumerate(examples):
+        outs[i] = generate_batch(model, ids[None].cuda(), enc[None].cuda(), tok, budget, keywords=())[0]
+    return outs
+
+
+def run_grouped(model, examples, tok, batch=8):
+    by_len = {}
+    for i, (ids, _, _) in enumerate(examples):
+        by_len.setdefault(ids.numel(), []).append(i)
+    outs, groups = {}, 0
+    for _, idx in sorted(by_len.items()):
+        for k in range(0, len(idx), batch):
+            grp = idx[k: k + batch]
+            groups += 1
+            ids = torch.stack([examples[i][0] for i in grp]).cuda()
+            enc = torch.stack([examples[i][1] for i in grp]).cuda()
+            rows = generate_batch(model, ids, enc, tok, max(examples[i][2] for i in grp), keywords=())
+            for i, r in zip(grp, rows):
+                outs[i] = r[: examples[i][0].numel() + examples[i][2]]
+    return outs, groups
+
+
+def run_inflight(model, examples, slots):
+    trace = []
+    outs = dict(generate_inflight(model, iter((ids, enc.cuda(), b) for ids, enc, b in examples), slots=slots, keywords=(), trace=trace))
+    return outs, sum(1 for e in trace if e[0] == "prefill")
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    r = fn()
+    torch.cuda.synchronize()
+    return r, time.perf_counter() - t0
+
+
+def decode_step_ms(model, examples, n_slots, steps=32):
+    """Ragged decode step with every slot active (prompts of the workload prefilled), wall clock over `steps` steps."""
+    eng = model.engine
+    eng.init_slots(n_slots)
+    rows = [examples[i % len(examples)] for i in range(n_slots)]
+    segs = [(k, 1, r[1].cuda()) for k, r in enumerate(rows)]
+    logits = eng.prefill_slots([r[0].cuda() for r in rows], segs, range(n_slots))
+    ids = logits.argmax(-1)
+    for _ in range(4):
+        ids, _, _ = eng.decode_slots(ids)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        ids, _, _ = eng.decode_slots(ids)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / steps * 1e3
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--examples", type=int, default=64)
+    ap.add_argument("--precision", default="split", choices=["split", "bf16"])
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_generate_inflight needs the GPU")
+    examples = make_examples(args.examples, args.seed)
+    max_seq = max(ids.numel() + b for ids, _, b in examples) + 8
+    model = RandomLlama(args.precision, 16, max_seq)
+    tok = _NoText()
+    gen_tokens = sum(b for _, _, b in examples)
+    warm = [(ids, enc, 4) for ids, enc, _ in examples[:16]]
+    run_batch1(model, warm[:2], tok)
+    run_grouped(model, warm, tok)
+    run_inflight(model, warm, 8)
+    run_inflight(model, warm, 16)
+    res = {"bench": "generate_inflight", "model": "llama2-7b dims, random weights", "precision": args.precision,
+           "examples": len(examples), "frames": {"240": sum(e[1].shape[0] == 240 for e in examples),
+                                                  "121": sum(e[1].shape[0] == 121 for e in examples)},
+           "prompt_tokens": [min(e[0].numel() for e in examples), max(e[0].numel() for e in examples)],
+           "generated_tokens": gen_tokens, "schedules": {}}
+    outs_a, t = timed(lambda: run_batch1(model, examples, tok))
+    res["schedules"]["batch1"] = {"s": round(t, 3), "clips_per_s": round(len(examples) / t, 3), "tokens_per_s": round(gen_tokens / t, 1)}
+    (outs_b, groups), t = timed(lambda: run_grouped(model, examples, tok))
+    res["schedules"]["grouped_b8"] = {"s": round(t, 3), "clips_per_s": round(len(examples) / t, 3), "tokens_per_s": round(gen_tokens / t, 1),
+                                      "generate_calls": groups, "mean_rows_per_call": round(len(examples) / groups, 2)}
+    for slots in (8, 16):
+        (outs_c, prefills), t = timed(lambda: run_inflight(model, examples, slots))
+        same = sum(torch.equal(outs_c[i].cpu(), outs_a[i].cpu()) for i in range(len(examples)))
+        assert all(outs_c[i].numel() == examples[i][0].numel() + examples[i][2] for i in range(len(examples)))
+        res["schedules"][f"inflight_{slots}"] = {"s": round(t, 3), "clips_per_s": round(len(examples) / t, 3),
+                                                 "tokens_per_s": round(gen_tokens / t, 1), "prefill_calls": prefills,
+                                                 "outputs_equal_to_batch1": same}
+    res["decode_step_ms"] = {str(n): round(decode_step_ms(model, examples, n), 3) for n in (1, 8, 16)}
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
