@@ -97,6 +97,12 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// Shifted cross-entropy: the row_loss of a row that does not count (ignore_index, a label outside [0, vocab), the last position).
+// A counted row's loss is >= 0, or NaN when its logits hold one, never this marker: the forward's mean and the backward test the
+// marker alone, so a NaN row stays in both (the loss reads NaN, as torch's does) and both divide by the same count.
+constexpr float CE_ROW_NOT_COUNTED = -1.0f;
+__device__ __forceinline__ bool ce_row_counted(float row_loss) { return row_loss != CE_ROW_NOT_COUNTED; }
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 typedef _Float16 half_t;

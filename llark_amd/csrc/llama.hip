@@ -814,7 +814,7 @@ static void attn_decode_lds_limit(int lds) {
 
 // ------------------------------------------------------------------------------------------
 // Shifted cross-entropy (m2t/models/llamav2.py:316-325): row (b,s), s < S-1, predicts labels[b][s+1];
-// ignore_index rows are skipped; loss = mean over the counted rows.
+// ignore_index rows are skipped; loss = mean over the counted rows (NaN when one of them is NaN, or when none counts).
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ logits, int ldl, int S, int vocab,
                                                       const long long* __restrict__ labels, long long ignore_index,
@@ -825,7 +825,7 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     long long tgt = (s + 1 < S) ? labels[(size_t)b * S + s + 1] : ignore_index;
     if (tgt == ignore_index || tgt < 0 || tgt >= vocab) {
-        if (threadIdx.x == 0) row_loss[row] = -1.0f;             // marker: not counted
+        if (threadIdx.x == 0) row_loss[row] = CE_ROW_NOT_COUNTED;
         return;
     }
     const float* lr = logits + (size_t)row * ldl;
@@ -853,7 +853,7 @@ __global__ __launch_bounds__(256) void ce_reduce_kernel(const float* __restrict_
     int n = 0;
     for (int i = threadIdx.x; i < rows; i += 256) {
         const float v = row_loss[i];
-        if (v >= 0.0f) { s += v; ++n; }
+        if (ce_row_counted(v)) { s += v; ++n; }                  // a NaN row counts: the mean is NaN, as torch reports it
     }
     ssum[threadIdx.x] = s;
     scnt[threadIdx.x] = n;

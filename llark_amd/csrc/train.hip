@@ -327,7 +327,7 @@ __global__ void swiglu_bwd_kernel(const float* __restrict__ gu, const float* __r
 
 // ------------------------------------------------------------------------------------------
 // cross-entropy backward on shifted logits: dlogits[row][v] = (softmax(logits[row])_v - [v == tgt]) / count for the
-// counted rows (row_loss >= 0, written by the forward kernel), zero otherwise; bf16, pitch ldd (pads zero).
+// counted rows (ce_row_counted: the forward kernel's marker), zero otherwise; bf16, pitch ldd (pads zero).
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ logits, int ldl, int S, int vocab,
                                                      const long long* __restrict__ labels, const float* __restrict__ row_loss,
@@ -338,7 +338,7 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
     const int row = b * S + s;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     bf16_t* out = dlogits + (size_t)row * ldd;
-    if (row_loss[row] < 0.0f) {
+    if (!ce_row_counted(row_loss[row])) {
         for (int c = threadIdx.x; c < ldd; c += 256) out[c] = (bf16_t)0.0f;
         return;
     }

@@ -103,10 +103,12 @@ def copy_weights_into_engine(eng, sd: Dict[str, torch.Tensor], origin: str = "st
         gu = L.wgu.view(d.intermediate_size // 32, 2, 32, d.hidden_size)
         gu[:, 0].copy_(gate.to(gu.device, gu.dtype).view(-1, 32, d.hidden_size))
         gu[:, 1].copy_(up.to(gu.device, gu.dtype).view(-1, 32, d.hidden_size))
+    eng.weights_changed_in_place()                            # fragment-major copies follow the new values
 
 
 def load_checkpoint(trainer, folder: str) -> int:
-    """Restores weights (kernel layout, in place), AdamW moments and the step counter; returns the step."""
+    """Restores weights (kernel layout, in place), AdamW moments and the step counter, then rebuilds the trainer's operands
+    derived from the weights (twins, lm_head operands, per-step caches); returns the step."""
     sd = torch.load(os.path.join(folder, "pytorch_model.bin"), map_location="cpu")
     copy_weights_into_engine(trainer.eng, sd, origin=folder)
     st = torch.load(os.path.join(folder, "trainer_state.pt"), map_location="cpu")
@@ -115,6 +117,7 @@ def load_checkpoint(trainer, folder: str) -> int:
     trainer.flat_m.copy_(st["exp_avg"])
     trainer.flat_v.copy_(st["exp_avg_sq"])
     trainer.step_count = int(st["step"])
+    trainer.refresh_derived()
     trainer.zero_grad()
     return trainer.step_count
 

@@ -238,6 +238,21 @@ class HipLlamaEngine:
         if self.lm_head is not None:
             ops.detach_frag(self.lm_head)
 
+    def weights_changed_in_place(self) -> None:
+        """The weights were overwritten in place (checkpoint.copy_weights_into_engine): every fragment-major copy attached to a
+        layer weight or to lm_head is re-packed into its own buffer, so the captured decode steps in ``_dec`` stay valid (every
+        buffer they read keeps its address) and are kept; the fused-RoPE q|k|v twins are dropped and rebuilt by the next prefill
+        that takes them.  A trainer's engine (``frag_weights`` False) carries none of these: its trainer refreshes its own."""
+        if not self.frag_weights:
+            return
+        for L in self.layers:
+            if L is not None:
+                for t in (L.wqkv, L.wo, L.wgu, L.wdown):
+                    ops.refresh_frag(t)
+                L.wqkv_rope = None
+        if self.lm_head is not None:
+            ops.refresh_frag(self.lm_head)
+
     def load_state_dict(self, sd) -> None:
         """HF / reference state-dict names (model.layers.N.self_attn.q_proj.weight, ..., model.mm_projector.*)."""
         d = self.dims

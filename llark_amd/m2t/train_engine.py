@@ -99,6 +99,7 @@ class HipLlamaTrainer:
         # llark_gemm16_fragw_rope_qkv (RoPE, head split and both cache writes in the epilogue) wherever the shape qualifies.
         self.twins: Dict[str, Tuple[torch.Tensor, torch.Tensor, int]] = {}
         self._frozen_wT: Dict[int, torch.Tensor] = {}
+        self._rope_order: Optional[torch.Tensor] = None          # gather index of the q|k|v twin's fused-RoPE row order
         self.use_twins = bool(optimizer_state) and os.environ.get("LLARK_TRAIN_TWINS", "1") != "0" and os.environ.get("LLARK_FRAG", "1") != "0"
         self.dw_fragw = os.environ.get("LLARK_TRAIN_DW_FRAGW", "1") != "0" and os.environ.get("LLARK_FRAG", "1") != "0"
         # the dW product on the 16x16x32 MFMA shape (csrc/gemm_bda16.hip): more flops per joule under the power limit
@@ -132,7 +133,6 @@ class HipLlamaTrainer:
         """Initial construction of the operand twins (afterwards llark_adamw_twins rewrites them with every optimizer step)."""
         eng, d = self.eng, self.eng.dims
         H = d.hidden_size
-        order = None
         for i, L in enumerate(eng.layers):
             for nm in ("wqkv", "wo", "wgu", "wdown"):
                 w = getattr(L, nm)
@@ -140,24 +140,45 @@ class HipLlamaTrainer:
                 if not ops.adamw_twins_takes(n, k) or not w.is_contiguous():
                     continue
                 rope_rows = 2 * H if (nm == "wqkv" and self.rope_fused) else 0
-                if rope_rows:
-                    if order is None:
-                        order = ops.rope_qkv_row_order(d.num_attention_heads, d.head_dim).to(w.device)
-                    wfrag = ops.pack_weight16_frag(w.index_select(0, order), n)
-                else:
-                    wfrag = ops.pack_weight16_frag(w, n)
-                    w._llark_frag = (wfrag, n, k)                 # ops.gemm16 takes the B-direct kernel for >= FRAG_MIN_ROWS rows
-                wT = ops.transposed16(w)                          # [k][n] (n % 64 == 0: no padding)
-                wtfrag = ops.pack_weight16_frag(wT, k)
-                del wT
-                self.twins[f"layers.{i}.{nm}"] = (wfrag, wtfrag, rope_rows)
-        # lm_head is frozen (m2t/models/llamav2.py:412-415): its twins are built once and never go stale
+                self.twins[f"layers.{i}.{nm}"] = self._pack_twins(w, rope_rows) + (rope_rows,)
+        # lm_head is frozen (m2t/models/llamav2.py:412-415): its twins go stale only when the weights are loaded from outside
         lm = eng.lm_head
         if lm is not None and lm.shape[1] % 64 == 0:
             ops.attach_frag(lm, lm.shape[0])
             wT = ops.transposed16(lm)                             # [H][V padded to 64]
             ops.attach_frag(wT, wT.shape[0])
             self._frozen_wT[lm.data_ptr()] = wT
+
+    def _pack_twins(self, w: torch.Tensor, rope_rows: int, wfrag: Optional[torch.Tensor] = None,
+                    wtfrag: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """W fragment-major (in the fused-RoPE row order when ``rope_rows``) and W^T fragment-major; into ``wfrag`` / ``wtfrag`` when given."""
+        n, k = w.shape
+        if rope_rows:
+            if self._rope_order is None:
+                self._rope_order = ops.rope_qkv_row_order(self.eng.dims.num_attention_heads, self.eng.dims.head_dim).to(w.device)
+            wfrag = ops.pack_weight16_frag(w.index_select(0, self._rope_order), n, out=wfrag)
+        else:
+            wfrag = ops.pack_weight16_frag(w, n, out=wfrag)
+            w._llark_frag = (wfrag, n, k)                         # ops.gemm16 takes the B-direct kernel for >= FRAG_MIN_ROWS rows
+        wT = ops.transposed16(w)                                  # [k][n] (n % 64 == 0: no padding)
+        wtfrag = ops.pack_weight16_frag(wT, k, out=wtfrag)
+        del wT
+        return wfrag, wtfrag
+
+    def refresh_derived(self) -> None:
+        """The weights were overwritten in place from outside the optimizer (checkpoint.load_checkpoint): every operand twin is
+        re-packed into its own buffers, the lm_head operands are rebuilt from ``eng.lm_head``, and the per-step caches are
+        invalidated as after an optimizer step.  Otherwise the next step would compute with the weights the twins were built from."""
+        params = dict(self.params)
+        for name, (wfrag, wtfrag, rope_rows) in self.twins.items():
+            self._pack_twins(params[name], rope_rows, wfrag, wtfrag)
+        lm = self.eng.lm_head
+        wT = self._frozen_wT.get(lm.data_ptr()) if lm is not None else None
+        if wT is not None:
+            ops.refresh_frag(lm)
+            ops.transpose16(lm, lm.stride(0), lm.shape[0], lm.shape[1], wT, wT.shape[1])
+            ops.refresh_frag(wT)
+        self._weights_changed()
 
     def _twin_of(self, w: torch.Tensor):
         name = self._pname.get(w.data_ptr())

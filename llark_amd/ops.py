@@ -444,6 +444,14 @@ def detach_frag(wt: torch.Tensor) -> None:
         del wt._llark_frag
 
 
+def refresh_frag(wt: torch.Tensor) -> None:
+    """`wt` was overwritten in place: re-pack its attached fragment-major copy into the same buffer (whatever recorded that
+    buffer's address -- a captured graph, a launch list -- stays valid).  No-op when nothing is attached."""
+    fr = getattr(wt, "_llark_frag", None)
+    if fr is not None:
+        pack_weight16_frag(wt, fr[1], out=fr[0])
+
+
 def _gemv_dma_takes(split: bool, m: int, kp: int) -> bool:
     """The shapes csrc/gemv_dma.hip takes (gemv_shape_ok there): activation fragments in registers or within 48 KiB of LDS."""
     if m < 1 or m > 4 or kp % 8 or kp > 12288:
@@ -703,10 +711,14 @@ def gemm16_rmsnorm_a(x: torch.Tensor, norm_w: torch.Tensor, eps: float, wt: torc
             "gemm16_rmsnorm_a")
 
 
-def pack_weight16_frag(wt: torch.Tensor, n: int) -> torch.Tensor:
-    """wt [>=n][kp] 16-bit (pack_weight16 output, kp % 64 == 0) -> fragment-major copy for gemm16_fragw."""
+def pack_weight16_frag(wt: torch.Tensor, n: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """wt [>=n][kp] 16-bit (pack_weight16 output, kp % 64 == 0) -> fragment-major copy for gemm16_fragw
+    (``out``: an existing copy of the same shape to re-pack in place)."""
     kp = wt.shape[1]
-    out = torch.empty((round_up(n, 32) * kp,), dtype=wt.dtype, device=wt.device)
+    if out is None:
+        out = torch.empty((round_up(n, 32) * kp,), dtype=wt.dtype, device=wt.device)
+    else:
+        assert out.dtype == wt.dtype and out.is_contiguous() and out.numel() == round_up(n, 32) * kp, "pack_weight16_frag: out does not fit"
     check(_lib.lib().llark_pack_weight16_frag(_dev(wt, "wt"), wt.stride(0), n, kp, _dev(out, "out"), _stream()), "pack_weight16_frag")
     return out
 

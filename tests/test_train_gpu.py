@@ -664,14 +664,15 @@ def test_swiglu_train_epilogues_match_the_two_launch_path(m, H, I):
     assert dgu_ref.float().abs().max().item() > 0
 
 
-def _setup_long(S=72, B=2, layers=2):
-    """Like _setup with sequences long enough for the fragment-major paths (>= 129 rows) and the fused-RoPE epilogue (S >= 32)."""
+def _setup_long(S=72, B=2, layers=2, seed=0):
+    """Like _setup with sequences long enough for the fragment-major paths (>= 129 rows) and the fused-RoPE epilogue (S >= 32).
+    ``seed`` draws other weights (lm_head included); the batch stays the same."""
     from llark_amd.m2t.engine import HipLlamaEngine, LlamaDims
     from oracle import llama_ref as LR
     V = 128
     spec = LR.LlamaSpec(hidden_size=256, intermediate_size=512, num_hidden_layers=layers, num_attention_heads=2, vocab_size=V,
                         mm_hidden_size=96, audio_start_token=V - 2, audio_end_token=V - 1, audio_patch_token=V - 3)
-    w = {k: _bf(v) for k, v in LR.make_weights(spec, seed=0, std=0.08).items()}
+    w = {k: _bf(v) for k, v in LR.make_weights(spec, seed=seed, std=0.08).items()}
     g = torch.Generator().manual_seed(6)
     F = 5
     ids = torch.stack([torch.tensor([1] + torch.randint(3, V - 3, (2 + b,), generator=g).tolist() + [V - 2] + [V - 3] * F + [V - 1]
