@@ -86,7 +86,10 @@ __global__ void scale_f32_kernel(float* __restrict__ x, long long n, float a) {
 
 __global__ void clamp_f32_kernel(float* __restrict__ x, long long n, float lim) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) x[i] = fminf(fmaxf(x[i], -lim), lim);
+    if (i < n) {
+        const float v = x[i];
+        x[i] = v != v ? v : fminf(fmaxf(v, -lim), lim);          // torch.clamp keeps a NaN (fminf / fmaxf would turn it into -lim)
+    }
 }
 
 // backward of the clamp: torch.clamp passes the gradient where -lim <= x <= lim (x = the value BEFORE the clamp), else 0

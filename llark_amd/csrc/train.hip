@@ -389,13 +389,28 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x,
     if ((threadIdx.x & 63) == 0 && acc != 0.0) atomicAdd(out, acc);
 }
 
-// out[c] (+)= sum_r x[r][c]
-__global__ void colsum_kernel(const float* __restrict__ x, int ld, int rows, int cols, float* __restrict__ out) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    float s = 0.0f;
-    for (int r = 0; r < rows; ++r) s += x[(size_t)r * ld + c];
-    out[c] += s;
+// out[c] += sum_r x[r][c].  A block owns 64 columns x COLSUM_ROWS rows: lane = column (256-byte row segments), each of the 4 waves
+// takes every 4th row into 8 interleaved partial sums, so no fp32 chain is longer than COLSUM_ROWS / 32 terms (one serial sum
+// over 16k+ same-sign terms drifts by ~sqrt(rows) ulps); the waves meet in LDS and the block issues one atomic per column.
+constexpr int COLSUM_ROWS = 1024;
+__global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ x, int ld, int rows, int cols, float* __restrict__ out) {
+    __shared__ float part[4][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + lane;
+    const int r0 = blockIdx.y * COLSUM_ROWS, r1 = min(rows, r0 + COLSUM_ROWS);
+    float acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (c < cols) {
+        const float* p = x + c;
+        int r = r0 + wv;
+        for (; r + 28 < r1; r += 32) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) acc[k] += p[(size_t)(r + 4 * k) * ld];
+        }
+        for (; r < r1; r += 4) acc[0] += p[(size_t)r * ld];
+    }
+    part[wv][lane] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+    __syncthreads();
+    if (wv == 0 && c < cols) atomicAdd(&out[c], (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]));
 }
 
 // gathers rows: dst[i][:] (+)= src[idx[i]][:]  (fp32)    /   scatter-add: dst[idx[i]][:] += src[i][:]
@@ -664,8 +679,8 @@ extern "C" int llark_sumsq_f32(const float* x, long long n, double* out, int acc
 }
 
 extern "C" int llark_colsum_f32(const float* x, int ld, int rows, int cols, float* out, llark_stream_t stream) {
-    LLARK_REQUIRE(x && out && rows > 0 && cols > 0, "colsum: bad arguments");
-    colsum_kernel<<<cdiv(cols, 256), 256, 0, (hipStream_t)stream>>>(x, ld, rows, cols, out);
+    LLARK_REQUIRE(x && out && rows > 0 && cols > 0 && ld >= cols && cdiv(rows, COLSUM_ROWS) <= 65535, "colsum: bad arguments");
+    colsum_kernel<<<dim3(cdiv(cols, 64), cdiv(rows, COLSUM_ROWS)), 256, 0, (hipStream_t)stream>>>(x, ld, rows, cols, out);
     return check_launch("colsum");
 }
 

@@ -1292,7 +1292,7 @@ def clap_logmel(wav: torch.Tensor, window: torch.Tensor, twiddle: torch.Tensor, 
 
 
 def split16_into(x: torch.Tensor, hi: torch.Tensor, lo: Optional[torch.Tensor]) -> None:
-    """split16 into caller-owned planes (row stride hi.stride(0) >= width; pad columns are the caller's to zero)."""
+    """split16 into caller-owned planes (row stride hi.stride(0) >= width; the pad columns [width, stride) are zero-filled)."""
     rows, width = x.shape
     check(_lib.lib().llark_split16(_DT[hi.dtype], _dev(x, "x", torch.float32), x.stride(0), rows, width, _dev(hi, "hi"),
                                    _opt(lo, "lo", hi.dtype), hi.stride(0), _stream()), "split16")

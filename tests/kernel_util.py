@@ -1,0 +1,63 @@
+"""Shared by the kernel-level GPU tests (test_mpt_kernels_gpu.py, test_clap_kernels_gpu.py): seeded generators, sentinel
+buffers with a bit-exact "nothing else was written" check, and the fp32 tolerance ``c * 2**-24 * B`` whose constant is measured
+on torch's own float32 CPU result of the same operation (never on the kernel under test)."""
+import torch
+
+from conftest import report_close
+
+EPS24 = 2.0 ** -24
+BF_SENTINEL = 0x7FB5            # a bf16 NaN with a recognisable payload
+
+
+def bf16_ulp(ref64):
+    """one bf16 ulp of ``ref64`` (numpy): 2**-8 |ref| for normal values, the format's absolute spacing 2**-133 below 2**-126"""
+    return 2.0 ** -8 * ref64.abs().numpy() + 2.0 ** -133
+
+
+def gen(*key):
+    return torch.Generator().manual_seed(hash(tuple(int(k) for k in key)) % (2 ** 31))
+
+
+def tol(name, torch32, ref64, bound):
+    """c * 2**-24 * B with c = max(16, 4 * torch's own worst ratio on these inputs)."""
+    ref64, bound = ref64.double(), bound.double()
+    err = (torch32.double() - ref64).abs()
+    pos = bound > 0
+    assert bool((err[~pos] == 0).all()), f"{name}: torch fp32 is off where the bound is 0"
+    r = float((err[pos] / (EPS24 * bound[pos])).max()) if pos.any() else 0.0
+    c = max(16.0, 4.0 * r)
+    return (c * EPS24 * bound).numpy(), r
+
+
+def check(name, got, ref64, atol, rtol=0.0, bound=None, r_torch=None):
+    got64 = got.detach().cpu().double()
+    if bound is not None:
+        pos = bound > 0
+        k = float(((got64 - ref64).abs()[pos] / (EPS24 * bound.double()[pos])).max()) if pos.any() else 0.0
+        print(f"[ratio] {name}: kernel {k:.3g} x 2^-24 B, torch fp32 {r_torch:.3g}")
+    return report_close(name, got64.numpy(), ref64.numpy(), atol, rtol)
+
+
+def bits(t):
+    return t.detach().cpu().contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
+
+
+def nan_buf(rows, ld):
+    return torch.full((rows, ld), float("nan"), dtype=torch.float32)
+
+
+def bf_sentinel(shape):
+    return torch.full(shape, BF_SENTINEL, dtype=torch.int16).view(torch.bfloat16)
+
+
+def assert_untouched(name, after, before, written):
+    """every element outside the boolean mask ``written`` is bit-identical to what it was before the launch"""
+    a, b = bits(after), bits(before)
+    keep = ~written
+    assert torch.equal(a[keep], b[keep]), f"{name}: {int((a[keep] != b[keep]).sum())} elements outside the output were written"
+
+
+def mask(shape, rows, c0, c1):
+    m = torch.zeros(shape, dtype=torch.bool)
+    m[:rows, c0:c1] = True
+    return m

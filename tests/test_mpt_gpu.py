@@ -222,3 +222,111 @@ def test_mpt_training_step_gradients_match_autograd(case):
     # the frozen-wte recipe (reference default) has no wte gradient slot
     tr2 = HipMptTrainer(_engine(spec, w, "bf16", max_batch=B, max_seq=64))
     assert "transformer.wte.weight" not in tr2.export_grads_ref()
+
+
+def _compare_grads_with_autograd(got, wp):
+    """the whole-model bound of test_mpt_training_step_gradients_match_autograd: per-tensor relative Frobenius error <= 5e-2 and
+    cosine >= 0.995; tensors whose reference gradient is < 1e-4 of the largest must be small on the GPU too"""
+    worst = {}
+    biggest = max(p_.grad.norm().item() for p_ in wp.values() if p_.grad is not None)
+    for name, gg in got.items():
+        a, b_ = gg.float().cpu().reshape(-1), wp[name].grad.reshape(-1)
+        if b_.norm().item() < 1e-4 * biggest:
+            assert a.norm().item() < 1e-2 * biggest, f"{name}: reference gradient ~0 but got norm {a.norm().item():.3e}"
+            continue
+        rel = ((a - b_).norm() / (b_.norm() + 1e-12)).item()
+        cos = (torch.dot(a, b_) / (a.norm() * b_.norm() + 1e-20)).item()
+        worst[name] = (rel, cos)
+        assert rel <= 5e-2 and cos >= 0.995, f"{name}: rel {rel:.3e} cos {cos:.5f}"
+    print("worst mpt grad rel errs:", sorted(((v[0], k) for k, v in worst.items()), reverse=True)[:3])
+    assert set(got) == set(wp)
+
+
+@pytest.mark.parametrize("V,S,bias", [(50371, 96, True), (50432, 93, False), (4099, 93, True), (4160, 96, False)],
+                         ids=["V50371-S96-bias", "V50432-S93", "V4099-S93-bias", "V4160-S96"])
+def test_mpt_training_step_at_1b_width_takes_the_recipe_branches(monkeypatch, V, S, bias):
+    """The gradient test at MPT-1B width (d_model 2048, 16 heads, expansion 4, qk_ln: layernorm_bwd NV = 8 on full rows and on
+    column slices, colsum / gelu_bwd at 8192 columns), 2 blocks.  B S = 192 rows (a multiple of 64: every dW goes through
+    gemm16_t on the operands as stored) and 186 rows (the transposed16 fallback); a vocabulary that is a multiple of 64 (dX of the
+    tied wte through gemm16_t) and one that is not (the padded fallback).  Which branch ran is asserted, not assumed."""
+    from llark_amd import ops
+    from llark_amd.m2t.mpt_train_engine import HipMptTrainer
+    from oracle import mpt_ref as MR
+    a0 = 50368 if V > 50000 else 4096                                       # the three audio tokens follow the text vocabulary
+    spec = MR.MptSpec(d_model=2048, n_heads=16, n_layers=2, expansion_ratio=4, vocab_size=V, max_seq_len=128, mm_hidden_size=64,
+                      qk_ln=True, no_bias=not bias, audio_start_token=a0, audio_end_token=a0 + 1, audio_patch_token=a0 + 2)
+    w = MR.make_weights(spec, seed=5, std=0.02)
+    g = torch.Generator().manual_seed(9)
+    B = 2
+    ids = torch.randint(0, a0, (B, S), generator=g)
+    ids[:, 2], ids[:, 3:7], ids[:, 7] = a0, a0 + 2, a0 + 1
+    aud = torch.randn(B, 4, 64, generator=g)
+    labels = ids.clone()
+    labels[:, :9] = -100
+    wp = {k: v.clone().requires_grad_(True) for k, v in w.items()}
+    ref = MR.forward(wp, spec, ids, aud, labels=labels)
+    ref["loss"].backward()
+    eng = _engine(spec, w, "bf16", max_batch=B, max_seq=128)
+    tr = HipMptTrainer(eng, train_wte=True)
+    calls = {"dw_t": 0, "dx_wte_t": 0, "transposed16": 0}
+    rows = B * S
+    real_t, real_tr = ops.gemm16_t, ops.transposed16
+
+    def counting_gemm16_t(a, wt, m, n, kp, trans_a, trans_b, c, **kw):
+        if trans_a and kp == rows:
+            calls["dw_t"] += 1
+        if not trans_a and kp == V:
+            calls["dx_wte_t"] += 1
+        return real_t(a, wt, m, n, kp, trans_a, trans_b, c, **kw)
+
+    def counting_transposed16(x, *a, **kw):
+        calls["transposed16"] += 1
+        return real_tr(x, *a, **kw)
+
+    monkeypatch.setattr(ops, "gemm16_t", counting_gemm16_t)
+    monkeypatch.setattr(ops, "transposed16", counting_transposed16)
+    loss = tr.forward_backward(ids.cuda(), [(b, 2, aud[b].cuda()) for b in range(B)], labels.cuda())
+    n_dw = 4 * spec.n_layers + 1                                            # Wqkv, out_proj, up, down per block + the tied wte
+    if rows % 64 == 0:
+        # wte's dW operand has V columns: gemm16_t needs V % 8 == 0, else that one product transposes
+        assert calls["dw_t"] == n_dw - (1 if V % 8 else 0), calls
+    else:
+        assert calls["dw_t"] == 0 and calls["transposed16"] >= 2 * n_dw, calls
+    assert calls["dx_wte_t"] == (1 if V % 64 == 0 else 0), calls
+    assert abs(loss.item() - ref["loss"].item()) <= 1e-2 * max(1.0, ref["loss"].item())
+    _compare_grads_with_autograd(tr.export_grads_ref(), wp)
+
+
+def test_mpt_trainer_accumulates_gradients_over_micro_batches():
+    """Two forward_backward calls without zero_grad leave the SUM of the two gradients in every slot (weights, biases, LayerNorm
+    gains and shifts, q/k LayerNorm, projector, tied wte): every dgamma / dbeta / bias kernel adds into its slot.  The two passes
+    are the same launches as the separate ones, so only the fp32 summation order of the atomically accumulated slots can differ:
+    <= 256 * 2**-24 of the larger addend per tensor (sums of <= 96 terms), while an overwritten slot would be off by a whole addend."""
+    from llark_amd.m2t.mpt_train_engine import HipMptTrainer
+    from oracle import mpt_ref as MR
+    spec = MR.MptSpec(**BASE, audio_start_token=93, audio_end_token=94, audio_patch_token=95, qk_ln=True, clip_qkv=3.0, no_bias=False,
+                      alibi_bias_max=4, logit_scale=0.5)
+    w = MR.make_weights(spec, seed=31, std=0.08)
+    g = torch.Generator().manual_seed(10)
+    B, S = 2, 24
+    batches = []
+    for _ in range(2):
+        ids = torch.randint(0, 90, (B, S), generator=g)
+        ids[:, 2], ids[:, 3:7], ids[:, 7] = 93, 95, 94
+        aud = torch.randn(B, 4, 64, generator=g)
+        labels = ids.clone()
+        labels[:, :9] = -100
+        batches.append((ids.cuda(), [(b, 2, aud[b].cuda()) for b in range(B)], labels.cuda()))
+    tr = HipMptTrainer(_engine(spec, w, "bf16", max_batch=B, max_seq=64), train_wte=True)
+    single = []
+    for bt in batches:
+        tr.zero_grad()
+        tr.forward_backward(*bt)
+        single.append({k: v.clone() for k, v in tr.grads.items()})
+    tr.zero_grad()
+    for bt in batches:
+        tr.forward_backward(*bt)
+    for name, got in tr.grads.items():
+        g1, g2 = single[0][name].double().cpu(), single[1][name].double().cpu()
+        assert g1.abs().max().item() > 0 or name.endswith("klb"), f"{name}: no gradient reached this slot"
+        report_close(f"accumulated {name}", got.double().cpu(), g1 + g2, 256 * 2.0 ** -24 * max(g1.abs().max().item(), g2.abs().max().item()))
