@@ -15,6 +15,7 @@ HBM layout:
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from dataclasses import dataclass
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -48,8 +49,26 @@ def interleave_gate_up(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
     return torch.stack((gate.view(I // 32, 32, H), up.view(I // 32, 32, H)), dim=1).reshape(2 * I, H).contiguous()
 
 
+def embed_splice(ids: torch.Tensor, table: torch.Tensor, h: torch.Tensor, audio_segments, proj_w, proj_b, split: bool) -> None:
+    """h[b * S + t] = table[ids[b, t]], then the projected frames of every (batch index, position of <audio_start>, frames fp32 (F, mm))
+    overwrite rows start + 1 .. start + F of their sequence (the splice of m2t/models/llamav2.py:141-222).  Shared with HipMptEngine."""
+    S = ids.shape[1]
+    ops.embed_gather(ids.reshape(-1).contiguous(), table, h)
+    for (b, start, frames) in audio_segments:
+        assert proj_w is not None, "mm_projector weights not loaded"
+        F = frames.shape[0]
+        a16, a16_lo = ops.split16(frames.to(device=h.device, dtype=torch.float32).contiguous(), torch.bfloat16, want_lo=split)
+        r0 = b * S + start + 1
+        ops.gemm16(a16, a16_lo, proj_w, proj_b, table.shape[1], ops.EPI_F32, c=h[r0: r0 + F])
+
+
 class _Layer:
     __slots__ = ("wqkv", "wo", "wgu", "wdown", "ln1", "ln2", "wqkv_rope")
+
+
+# What one prefill launch sequence works on: `nb` batch rows of the workspace (the whole batch, or one half per stream) and the KV-cache
+# slot of the first of them.  The *_lo planes are None in the "bf16" flow.
+_Rows = namedtuple("_Rows", "nb slot0 h qkv x16 x16_lo q q_lo att att_lo act act_lo")
 
 
 class HipLlamaEngine:
@@ -87,50 +106,29 @@ class HipLlamaEngine:
         self.k_cache = self.vt_cache = self.k_cache_lo = self.vt_cache_lo = None
         self.cur_len = 0
         self.cur_batch = 0
-        # graph-captured decode step (one hipGraph per batch size; position read from device memory)
-        # o_proj / down_proj + following RMSNorm in one launch ("last workgroup done" tail).  Bit-identical, but OFF by
-        # default.  Round 1 fenced with __threadfence() in every workgroup (an L2 write-back + invalidate each on the 8-XCD
-        # part: ~65 us per launch, 10.1 vs 5.9 ms per decode step); with write-through stores + a relaxed ticket + ONE
-        # acquire in the last workgroup (round 2) the tail is cheap but still serial: 4.34 vs 3.97 ms per token at B = 1 --
-        # the last workgroup normalises alone while the chip idles, which costs more than the 5 us rmsnorm launch it removes.
+        # The knobs of the launch sequences: what each does and its default.  How each was measured and why the opt-ins lost: DESIGN.md 7(g).
+        # decode: o_proj / down_proj + the FOLLOWING RMSNorm in one launch ("last workgroup done" tail); bit-identical, slower: default off
         self.fuse_decode_norm = os.environ.get("LLARK_DECODE_FUSE_NORM", "0") == "1"
-        # RMSNorm fused INTO the consuming decode GEMM (each workgroup re-derives the row scales): bit-identical, saves
-        # two launches per layer (+ the final norm before lm_head).  Measured: B = 8 split 5.89 vs 6.04 ms per step, but
-        # B = 8 single-pass 5.26 vs 4.85 ms and B = 1 split 492 vs 480 ms per 64-token generate.  Why it cannot win: every
-        # one of the ~768 workgroups of a decode GEMM re-normalises and re-splits its activation fragments (~50 VALU
-        # instructions per k-step and wave), so the fused kernel turns VALU-bound (+15 us per launch, more than the
-        # rmsnorm launch it removes); hoisting the weight loads above the scale derivation and batching the raw loads
-        # before the conversions (tried, round 1) changed nothing.  Opt-in (LLARK_DECODE_FUSE_NORM_A=1).
-        # Round 3: the LDS-DMA streaming Linear (csrc/gemv_dma.hip) holds the whole activation row in every wave's registers, so
-        # it derives rstd and the hi / lo planes itself under the weight stream that is already flowing: that form (B = 1, weights
-        # >= 64 MB: q/k/v, gate/up, lm_head) is the default ("auto"); "1" forces the fusion for every decode shape (the MFMA skinny
-        # kernel's per-k-step form for the others), "0" switches it off.
-        self.fuse_decode_norm_a = os.environ.get("LLARK_DECODE_FUSE_NORM_A", "auto")      # property: also takes True / False
-        self.decode_graph = os.environ.get("LLARK_DECODE_GRAPH", "0") == "1"      # measured: no gain on ROCm 7.2 (kernel boundaries remain), opt-in
-        # decode step as a recorded host launch list over static buffers (ops.LaunchList): removes the per-launch Python cost
+        # decode: RMSNorm INSIDE the consuming GEMM; bit-identical.  "auto" (default) = where the LDS-DMA streaming Linear takes it (B = 1,
+        # weights >= 64 MB: q/k/v, gate/up, lm_head), "1" = every decode shape, "0" = never.  A property: also takes True / False.  The
+        # per-k-step form of "1": B = 8 split 5.89 vs 6.04 ms per step, B = 8 bf16 5.26 vs 4.85, B = 1 split 492 vs 480 ms per 64 tokens
+        self.fuse_decode_norm_a = os.environ.get("LLARK_DECODE_FUSE_NORM_A", "auto")
+        # decode step as ONE hipGraph per batch size, position read from device memory; no gain on ROCm 7.2: default off
+        self.decode_graph = os.environ.get("LLARK_DECODE_GRAPH", "0") == "1"
+        # decode step as a recorded host launch list over static buffers (ops.LaunchList): removes the per-launch Python cost; default off
         self.decode_replay = os.environ.get("LLARK_DECODE_REPLAY", "0") == "1"
-        # decode: RoPE + KV-cache append inside the attention launch (one launch per layer fewer); LLARK_DECODE_FUSE_ROPE=0 = two launches
+        # decode: RoPE + KV-cache append inside the attention launch (one launch per layer fewer); default on, "0" = two launches
         self.fuse_decode_rope = os.environ.get("LLARK_DECODE_FUSE_ROPE", "1") != "0"
-        # round 6: batch-1 decode with o_proj launched on a side stream while the attention still runs (it fills its weight ring and spins on
-        # the attention's arrival counter) and gate/up filling its ring while o_proj runs (llark_gemv16_dma_chain); opt-in until measured
+        # batch-1 decode with o_proj on a side stream under the attention and gate/up under o_proj (_decode_layers_chained); default off
         self.decode_chain = os.environ.get("LLARK_DECODE_CHAIN", "0") == "1"
         self._chain = None
-        # prefill: RoPE + head split + K / V^T cache writes inside the q|k|v GEMM's epilogue (llark_gemm16_fragw_rope_qkv: no fp32 qkv
-        # tensor, no rope_split_kernel launch).  "auto" (default) = fused wherever the two-launch path runs the same whole-tile kernel,
-        # so q / K / V^T and the logits stay BIT-equal (tests/test_llama_gpu.py); "1" = fused for every prefill of >= 32 positions;
-        # "0" = two launches.  Measured at 7B, 8 x 371 (profiles/r04_rope_fuse_ab_v2.txt, same engine, interleaved): forward 42.48 ->
-        # 40.97 ms bf16, 79.03 -> 77.82 ms split.  (The first version stored the V tiles straight from the accumulator lanes -- 64
-        # two-byte pieces on 64 cache lines per instruction -- and lost what the removed launch gained: 42.63 -> 42.24 / 79.10 -> 80.31,
-        # profiles/r04_rope_fuse_ab_v1.txt; the V tiles now go through a wave-private LDS transposition.)  Costs a second fragment-major
-        # copy of the q|k|v weight in the epilogue's row order (+ 3 H^2 x 2 bytes per layer: 3.2 GB at 7B), built at load time unless "0".
+        # prefill: RoPE + head split + K / V^T cache writes in the q|k|v GEMM's epilogue.  "auto" (default) = wherever the two-launch path
+        # runs the same whole-tile kernel, so results stay BIT-equal; "1" = every prefill of >= 32 positions; "0" = two launches.  Costs a
+        # second fragment-major q|k|v weight per layer (3.2 GB at 7B), built lazily (_rope_weight)
         self.fuse_prefill_rope = os.environ.get("LLARK_PREFILL_FUSE_ROPE", "auto")
         if self.fuse_prefill_rope not in ("0", "1", "auto"):
             raise ValueError(f"LLARK_PREFILL_FUSE_ROPE must be 0, 1 or auto, got {self.fuse_prefill_rope!r}")
-        # prefill of an even batch as TWO half-batches on two HIP streams (round 5; LLARK_PREFILL_STREAMS=2, default 1 until measured):
-        # every kernel of the layer stack leaves part of the chip idle in its last round of tiles (M = 8 x 371 = 2968 rows: q|k|v 2.25
-        # rounds of the 512 resident workgroups, o_proj / down_proj 0.75) and none of them overlaps its successor on ONE stream; two
-        # independent half-batches let the hardware dispatcher fill the tail of one stream's kernel with the other stream's workgroups.
-        # Same kernels, same per-row arithmetic; the K cuts of o_proj / down_proj follow the half-batch's tile count (see ops.gemm16_fragw).
+        # prefill of an even batch as TWO half-batches on two HIP streams (_prefill_two_streams); default 1 until measured
         self.prefill_streams = int(os.environ.get("LLARK_PREFILL_STREAMS", "1"))
         if self.prefill_streams not in (1, 2):
             raise ValueError(f"LLARK_PREFILL_STREAMS must be 1 or 2, got {self.prefill_streams}")
@@ -327,91 +325,115 @@ class HipLlamaEngine:
         H = self.dims.hidden_size
         return ops.gemm16_fragw_whole_tiles(self.split, ops.EPI_F32, batch * s, 3 * H, H)
 
-    # ---- forward -------------------------------------------------------------------------------
+    # ---- forward: shared pieces ------------------------------------------------------------------
+    def _kv_views(self, i: int, c0: int, c1: int):
+        """kc, vc, kcl, vcl: the K / V^T cache of layer i for slots c0 .. c1 - 1 (the lo planes are None in the "bf16" flow)."""
+        kc, vc = self.k_cache[i, c0:c1], self.vt_cache[i, c0:c1]
+        kcl = self.k_cache_lo[i, c0:c1] if self.split else None
+        vcl = self.vt_cache_lo[i, c0:c1] if self.split else None
+        if not kc.is_contiguous():            # batch smaller than the allocated cache
+            raise ops._lib.LlarkHipError("KV cache batch mismatch: call reset(batch) before prefill")
+        return kc, vc, kcl, vcl
+
+    def _epi_swiglu(self) -> int:
+        return ops.EPI_SWIGLU_SPLIT if self.split else ops.EPI_SWIGLU16
+
+    def _norm_gemm_takes(self, batch: int, n: int) -> bool:
+        """Does the decode Linear [batch] x [n][H] run with the preceding RMSNorm inside its launch (fuse_decode_norm_a)?"""
+        mode = self.fuse_decode_norm_a
+        return mode == "1" or (mode == "auto" and ops.gemv_dma_rmsnorm_takes(batch, n, self.dims.hidden_size))
+
+    def _head(self, ws, logits: torch.Tensor, normed: bool, may_fuse: bool) -> None:
+        """Final norm + lm_head on the workspace rows.  normed: ws["x16"] already holds the normalised rows; may_fuse: the norm may
+        run inside the streaming GEMM where that takes the shape (the graph / replay step never asks for it)."""
+        d, h = self.dims, ws["h"]
+        if may_fuse and not normed and self._norm_gemm_takes(h.shape[0], d.vocab_size):
+            ops.gemm16_rmsnorm_a(h, self.norm, d.rms_norm_eps, self.lm_head, d.vocab_size, ops.EPI_F32, self.split, c=logits)
+            return
+        if not normed:
+            ops.rmsnorm_bf16(h, self.norm, d.rms_norm_eps, ws["x16"], ws["x16_lo"])
+        ops.gemm16(ws["x16"], ws["x16_lo"], self.lm_head, None, d.vocab_size, ops.EPI_F32, c=logits)
+
+    def _head_rows(self, hl: torch.Tensor) -> torch.Tensor:
+        """Final norm + lm_head on gathered rows hl fp32 [n][H] -> fp32 logits [n][V]."""
+        d, n = self.dims, hl.shape[0]
+        x16 = torch.empty((n, d.hidden_size), dtype=torch.bfloat16, device=self.device)
+        x16_lo = torch.empty_like(x16) if self.split else None
+        ops.rmsnorm_bf16(hl, self.norm, d.rms_norm_eps, x16, x16_lo)
+        logits = torch.empty((n, d.vocab_size), dtype=torch.float32, device=self.device)
+        ops.gemm16(x16, x16_lo, self.lm_head, None, d.vocab_size, ops.EPI_F32, c=logits)
+        return logits
+
     def _layers_forward(self, ws, batch: int, s: int, pos0: int, num_layers: Optional[int] = None, pos_dev=None, hidden_sink=None,
                         slot0: int = 0, pos_rows=None) -> bool:
-        """Runs the decoder layers on ws["h"].  Returns True when ws["x16"] already holds RMSNorm_final(h) (the fused
-        decode path normalises inside the producing GEMM), False when the caller still has to apply the final norm.
-        slot0: first KV-cache slot of these batch rows (ragged mode); pos_rows: int32 [batch] device positions of a ragged
-        decode step (s = 1), one per slot."""
-        d = self.dims
-        H, I, nh, hd = d.hidden_size, d.intermediate_size, d.num_attention_heads, d.head_dim
-        h = ws["h"]
-        n_layers = d.num_hidden_layers if num_layers is None else num_layers
-        sp = self.split
+        """Runs the decoder layers on ws["h"]: the decode launch sequence for one token per sequence (s == 1, also at pos0 == 0), the
+        prefill one otherwise.  Returns True when ws["x16"] already holds RMSNorm_final(h) (the fused decode path normalises inside
+        the producing GEMM), False when the caller still has to apply the final norm.
+        slot0: first KV-cache slot of these batch rows (ragged mode); pos_dev: int32 [1] device position of a graph-capturable
+        decode step; pos_rows: int32 [batch] device positions of a ragged decode step, one per slot."""
+        n_layers = self.dims.num_hidden_layers if num_layers is None else num_layers
         if slot0 < 0 or slot0 + batch > self.k_cache.shape[1]:
             raise ValueError(f"KV-cache slots {slot0} .. {slot0 + batch - 1} outside the {self.k_cache.shape[1]} allocated")
-        # decode (one token per sequence): o_proj / down_proj carry the FOLLOWING RMSNorm in their launch
-        fused = s == 1 and batch <= 16 and n_layers > 0 and self.fuse_decode_norm and H <= 8192 and hidden_sink is None
-        norm_a = (s == 1 and batch <= 16 and not fused and H % 32 == 0 and
-                  (self.fuse_decode_norm_a == "1" or (self.fuse_decode_norm_a == "auto" and ops.gemv_dma_rmsnorm_takes(batch, 3 * H, H))))
+        if s == 1:
+            return self._decode_layers(ws, batch, pos0, n_layers, pos_dev, hidden_sink, slot0, pos_rows)
+        self._prefill_layers(ws, batch, s, pos0, n_layers, hidden_sink, slot0)
+        return False
+
+    # ---- forward: decode ---------------------------------------------------------------------------
+    def _decode_layers(self, ws, batch: int, pos0: int, n_layers: int, pos_dev, hidden_sink, slot0: int, pos_rows) -> bool:
+        """The decoder layers of a decode step.  Decided once, here: `fused` (o_proj / down_proj carry the FOLLOWING RMSNorm in their
+        launch), `norm_a` (RMSNorm inside the consuming weight-streaming GEMM) and the attention form -- "rows" (ragged: each slot at its
+        own position), "rope" (RoPE + cache append inside the attention launch), "dpos" (position in device memory, graph-capturable)
+        or "plain" (rope_split_heads + attn_decode)."""
+        d = self.dims
+        H, I, nh, hd, eps, sp = d.hidden_size, d.intermediate_size, d.num_attention_heads, d.head_dim, d.rms_norm_eps, self.split
+        fused = batch <= 16 and n_layers > 0 and self.fuse_decode_norm and H <= 8192 and hidden_sink is None
+        norm_a = batch <= 16 and not fused and H % 32 == 0 and self._norm_gemm_takes(batch, 3 * H)
         if fused:
-            ops.rmsnorm_bf16(h, self.layers[0].ln1, d.rms_norm_eps, ws["x16"], ws["x16_lo"])
-        rope_fused = s > 1 and pos_dev is None and self._prefill_rope_fused(batch, s)
-        if rope_fused:
-            rope_fused = all(self._rope_weight(self.layers[i]) is not None for i in range(n_layers))
-        if (self.prefill_streams == 2 and rope_fused and batch >= 2 and batch % 2 == 0 and self._prefill_rope_fused(batch // 2, s)
-                and hidden_sink is None and not torch.cuda.is_current_stream_capturing()):
-            self._prefill_two_streams(ws, batch, s, pos0, n_layers, slot0)
-            return False
-        if (self.decode_chain and s == 1 and batch == 1 and norm_a and self.fuse_decode_rope and pos_dev is None and hidden_sink is None
+            ops.rmsnorm_bf16(ws["h"], self.layers[0].ln1, eps, ws["x16"], ws["x16_lo"])
+        if (self.decode_chain and batch == 1 and norm_a and self.fuse_decode_rope and pos_dev is None and hidden_sink is None
                 and not fused and H <= 4096 and slot0 == 0 and pos_rows is None and not torch.cuda.is_current_stream_capturing()):
             self._decode_layers_chained(ws, pos0, n_layers)
             return False
+        attn = "rows" if pos_rows is not None else "rope" if self.fuse_decode_rope else "dpos" if pos_dev is not None else "plain"
+        pos = pos_rows if attn == "rows" else pos_dev if pos_dev is not None else pos0
+        epi_gu, cos, sin = self._epi_swiglu(), self.cos, self.sin
+        h, qkv, x16, x16l, q, ql = ws["h"], ws["qkv"], ws["x16"], ws["x16_lo"], ws["q"], ws["q_lo"]
+        att, attl, act, actl = ws["att"], ws["att_lo"], ws["act"], ws["act_lo"]
         for i in range(n_layers):
             L = self.layers[i]
             if hidden_sink is not None:                       # HF output_hidden_states: the stream as it ENTERS every layer
-                hidden_sink.append(h.view(batch, s, H).clone())
-            kc, vc = self.k_cache[i, slot0: slot0 + batch], self.vt_cache[i, slot0: slot0 + batch]
-            kcl = self.k_cache_lo[i, slot0: slot0 + batch] if sp else None
-            vcl = self.vt_cache_lo[i, slot0: slot0 + batch] if sp else None
-            if not kc.is_contiguous():            # batch smaller than the allocated cache
-                raise ops._lib.LlarkHipError("KV cache batch mismatch: call reset(batch) before prefill")
-            if rope_fused:                           # prefill: RoPE / head split / cache writes in the q|k|v epilogue
-                ops.rmsnorm_bf16(h, L.ln1, d.rms_norm_eps, ws["x16"], ws["x16_lo"])
-                ops.gemm16_fragw_rope_qkv(ws["x16"], ws["x16_lo"], L.wqkv_rope, H, batch, s, nh, pos0, self.cos, self.sin, ws["q"], kc, vc,
-                                          ws["q_lo"], kcl, vcl)
-            elif norm_a:                             # decode: RMSNorm fused into the consuming weight-streaming GEMM
-                ops.gemm16_rmsnorm_a(h, L.ln1, d.rms_norm_eps, L.wqkv, 3 * H, ops.EPI_F32, sp, c=ws["qkv"])
+                hidden_sink.append(h.view(batch, 1, H).clone())
+            kc, vc, kcl, vcl = self._kv_views(i, slot0, slot0 + batch)
+            if norm_a:
+                ops.gemm16_rmsnorm_a(h, L.ln1, eps, L.wqkv, 3 * H, ops.EPI_F32, sp, c=qkv)
             else:
                 if not fused:
-                    ops.rmsnorm_bf16(h, L.ln1, d.rms_norm_eps, ws["x16"], ws["x16_lo"])
-                ops.gemm16(ws["x16"], ws["x16_lo"], L.wqkv, None, 3 * H, ops.EPI_F32, c=ws["qkv"])
-            if rope_fused:
-                ops.attn_prefill(ws["q"], kc, vc, batch, s, nh, hd, pos0, ws["att"], ws["q_lo"], kcl, vcl, ws["att_lo"])
-            elif pos_rows is not None:               # ragged decode step: RoPE / cache append / attention at each slot's own position
-                ops.attn_decode_rope_rows(ws["qkv"], batch, nh, hd, pos_rows, self.cos, self.sin, kc, vc, ws["att"], kcl, vcl, ws["att_lo"])
-            elif s == 1 and self.fuse_decode_rope:
-                ops.attn_decode_rope(ws["qkv"], batch, nh, hd, pos_dev if pos_dev is not None else pos0, self.cos, self.sin, kc, vc,
-                                     ws["att"], kcl, vcl, ws["att_lo"])
-            elif pos_dev is not None:               # decode step, position in device memory (graph-capturable)
-                ops.rope_split_heads_dpos(ws["qkv"], batch, nh, hd, pos_dev, self.cos, self.sin, ws["q"], kc, vc,
-                                          ws["q_lo"], kcl, vcl)
-                ops.attn_decode_dpos(ws["q"], kc, vc, batch, nh, hd, pos_dev, ws["att"], ws["q_lo"], kcl, vcl, ws["att_lo"])
+                    ops.rmsnorm_bf16(h, L.ln1, eps, x16, x16l)
+                ops.gemm16(x16, x16l, L.wqkv, None, 3 * H, ops.EPI_F32, c=qkv)
+            if attn == "rows":
+                ops.attn_decode_rope_rows(qkv, batch, nh, hd, pos, cos, sin, kc, vc, att, kcl, vcl, attl)
+            elif attn == "rope":
+                ops.attn_decode_rope(qkv, batch, nh, hd, pos, cos, sin, kc, vc, att, kcl, vcl, attl)
+            elif attn == "dpos":
+                ops.rope_split_heads_dpos(qkv, batch, nh, hd, pos, cos, sin, q, kc, vc, ql, kcl, vcl)
+                ops.attn_decode_dpos(q, kc, vc, batch, nh, hd, pos, att, ql, kcl, vcl, attl)
             else:
-                ops.rope_split_heads(ws["qkv"], batch, s, nh, hd, pos0, self.cos, self.sin, ws["q"], kc, vc,
-                                     ws["q_lo"], kcl, vcl)
-                if s == 1:
-                    ops.attn_decode(ws["q"], kc, vc, batch, nh, hd, pos0 + 1, ws["att"], ws["q_lo"], kcl, vcl, ws["att_lo"])
-                else:
-                    ops.attn_prefill(ws["q"], kc, vc, batch, s, nh, hd, pos0, ws["att"], ws["q_lo"], kcl, vcl, ws["att_lo"])
+                ops.rope_split_heads(qkv, batch, 1, nh, hd, pos, cos, sin, q, kc, vc, ql, kcl, vcl)
+                ops.attn_decode(q, kc, vc, batch, nh, hd, pos + 1, att, ql, kcl, vcl, attl)
             if fused:
-                ops.gemm16_resid_rmsnorm(ws["att"], ws["att_lo"], L.wo, h, L.ln2, d.rms_norm_eps, ws["x16"], ws["x16_lo"])
-            else:
-                ops.gemm16(ws["att"], ws["att_lo"], L.wo, None, H, ops.EPI_RESID, c=h, resid=h)
-                if not norm_a:
-                    ops.rmsnorm_bf16(h, L.ln2, d.rms_norm_eps, ws["x16"], ws["x16_lo"])
-            if norm_a:
-                ops.gemm16_rmsnorm_a(h, L.ln2, d.rms_norm_eps, L.wgu, 2 * I, ops.EPI_SWIGLU_SPLIT if sp else ops.EPI_SWIGLU16, sp,
-                                     out_hi=ws["act"], out_lo=ws["act_lo"])
-            else:
-                ops.gemm16(ws["x16"], ws["x16_lo"], L.wgu, None, 2 * I, ops.EPI_SWIGLU_SPLIT if sp else ops.EPI_SWIGLU16,
-                           out_hi=ws["act"], out_lo=ws["act_lo"])
-            if fused:
+                ops.gemm16_resid_rmsnorm(att, attl, L.wo, h, L.ln2, eps, x16, x16l)
+                ops.gemm16(x16, x16l, L.wgu, None, 2 * I, epi_gu, out_hi=act, out_lo=actl)
                 nxt = self.layers[i + 1].ln1 if i + 1 < n_layers else self.norm
-                ops.gemm16_resid_rmsnorm(ws["act"], ws["act_lo"], L.wdown, h, nxt, d.rms_norm_eps, ws["x16"], ws["x16_lo"])
+                ops.gemm16_resid_rmsnorm(act, actl, L.wdown, h, nxt, eps, x16, x16l)
+                continue
+            ops.gemm16(att, attl, L.wo, None, H, ops.EPI_RESID, c=h, resid=h)
+            if norm_a:
+                ops.gemm16_rmsnorm_a(h, L.ln2, eps, L.wgu, 2 * I, epi_gu, sp, out_hi=act, out_lo=actl)
             else:
-                ops.gemm16(ws["act"], ws["act_lo"], L.wdown, None, H, ops.EPI_RESID, c=h, resid=h)
+                ops.rmsnorm_bf16(h, L.ln2, eps, x16, x16l)
+                ops.gemm16(x16, x16l, L.wgu, None, 2 * I, epi_gu, out_hi=act, out_lo=actl)
+            ops.gemm16(act, actl, L.wdown, None, H, ops.EPI_RESID, c=h, resid=h)
         return fused
 
     def _decode_layers_chained(self, ws, pos0: int, n_layers: int) -> None:
@@ -426,7 +448,7 @@ class HipLlamaEngine:
         Same kernels, same arithmetic: results equal the unchained path."""
         d = self.dims
         H, I, nh, hd = d.hidden_size, d.intermediate_size, d.num_attention_heads, d.head_dim
-        sp = self.split
+        sp, epi_gu = self.split, self._epi_swiglu()
         if self._chain is None or self._chain["layers"] != n_layers:
             self._chain = {"layers": n_layers, "cnt": torch.zeros((2 * n_layers,), dtype=torch.int32, device=self.device), "epoch": 0,
                            "side": torch.cuda.Stream(device=self.device), "ev": torch.cuda.Event(), "blocks_o": ops.gemv16_dma_blocks(ops.EPI_RESID, H)}
@@ -437,9 +459,7 @@ class HipLlamaEngine:
         h = ws["h"]
         for i in range(n_layers):
             L = self.layers[i]
-            kc, vc = self.k_cache[i, :1], self.vt_cache[i, :1]
-            kcl = self.k_cache_lo[i, :1] if sp else None
-            vcl = self.vt_cache_lo[i, :1] if sp else None
+            kc, vc, kcl, vcl = self._kv_views(i, 0, 1)
             a_done, o_done = cnt[2 * i: 2 * i + 1], cnt[2 * i + 1: 2 * i + 2]
             ops.gemm16_rmsnorm_a(h, L.ln1, d.rms_norm_eps, L.wqkv, 3 * H, ops.EPI_F32, sp, c=ws["qkv"])
             ev.record(main)
@@ -448,38 +468,65 @@ class HipLlamaEngine:
             with torch.cuda.stream(side):
                 ops.gemv16_dma_chain(L.wo, H, ops.EPI_RESID, sp, a_hi=ws["att"], a_lo=ws["att_lo"], c=h, resid=h,
                                      wait=a_done, wait_target=ep * nh, signal=o_done)
-            ops.gemv16_dma_chain(L.wgu, 2 * I, ops.EPI_SWIGLU_SPLIT if sp else ops.EPI_SWIGLU16, sp, x=h, norm_w=L.ln2, eps=d.rms_norm_eps,
+            ops.gemv16_dma_chain(L.wgu, 2 * I, epi_gu, sp, x=h, norm_w=L.ln2, eps=d.rms_norm_eps,
                                  out_hi=ws["act"], out_lo=ws["act_lo"], wait=o_done, wait_target=ep * ch["blocks_o"])
             ops.gemm16(ws["act"], ws["act_lo"], L.wdown, None, H, ops.EPI_RESID, c=h, resid=h)
         main.wait_stream(side)                                   # (the data dependency is already met through O_i: this is for the allocator's sake)
 
-    def _prefill_layer_rows(self, ws, L, i: int, b0: int, b1: int, s: int, pos0: int, slot0: int = 0) -> None:
-        """One decoder layer of a PREFILL on batch rows b0 .. b1 - 1 (the fused-RoPE path of _layers_forward on row slices); their
-        KV-cache slots start at slot0 + b0."""
-        d = self.dims
-        H, I, nh, hd = d.hidden_size, d.intermediate_size, d.num_attention_heads, d.head_dim
-        sp, nb = self.split, b1 - b0
-        r0, r1 = b0 * s, b1 * s
-        h = ws["h"][r0:r1]
-        x16, att, act, q = ws["x16"][r0:r1], ws["att"][r0:r1], ws["act"][r0:r1], ws["q"][b0:b1]
-        x16l = ws["x16_lo"][r0:r1] if sp else None
-        attl = ws["att_lo"][r0:r1] if sp else None
-        actl = ws["act_lo"][r0:r1] if sp else None
-        ql = ws["q_lo"][b0:b1] if sp else None
-        c0, c1 = slot0 + b0, slot0 + b1
-        kc, vc = self.k_cache[i, c0:c1], self.vt_cache[i, c0:c1]
-        kcl = self.k_cache_lo[i, c0:c1] if sp else None
-        vcl = self.vt_cache_lo[i, c0:c1] if sp else None
-        ops.rmsnorm_bf16(h, L.ln1, d.rms_norm_eps, x16, x16l)
-        ops.gemm16_fragw_rope_qkv(x16, x16l, L.wqkv_rope, H, nb, s, nh, pos0, self.cos, self.sin, q, kc, vc, ql, kcl, vcl)
-        ops.attn_prefill(q, kc, vc, nb, s, nh, hd, pos0, att, ql, kcl, vcl, attl)
-        ops.gemm16(att, attl, L.wo, None, H, ops.EPI_RESID, c=h, resid=h)
-        ops.rmsnorm_bf16(h, L.ln2, d.rms_norm_eps, x16, x16l)
-        ops.gemm16(x16, x16l, L.wgu, None, 2 * I, ops.EPI_SWIGLU_SPLIT if sp else ops.EPI_SWIGLU16, out_hi=act, out_lo=actl)
-        ops.gemm16(act, actl, L.wdown, None, H, ops.EPI_RESID, c=h, resid=h)
+    def _decode_body(self, st) -> None:
+        """One decode step on static buffers: ids -> logits, new K/V written at *pos.  Never takes the norm-fused lm_head."""
+        ws = st["ws"]
+        ops.embed_gather(st["ids"].view(-1), self.embed, ws["h"])
+        normed = self._layers_forward(ws, st["ids"].shape[0], 1, 0, None, pos_dev=st["pos"])
+        self._head(ws, st["logits"], normed, may_fuse=False)
+
+    # ---- forward: prefill --------------------------------------------------------------------------
+    def _rows(self, ws, b0: int, b1: int, s: int, slot0: int):
+        """Batch rows b0 .. b1 - 1 of the workspace (a full-range slice is the tensor itself to the kernels: same pointer, same shape);
+        their KV-cache slots start at slot0 + b0."""
+        r, b = slice(b0 * s, b1 * s), slice(b0, b1)
+
+        def cut(name, sl):
+            return ws[name][sl] if ws[name] is not None else None
+
+        return _Rows(b1 - b0, slot0 + b0, ws["h"][r], ws["qkv"][r], ws["x16"][r], cut("x16_lo", r), ws["q"][b], cut("q_lo", b),
+                     ws["att"][r], cut("att_lo", r), ws["act"][r], cut("act_lo", r))
+
+    def _prefill_layer(self, i: int, v, s: int, pos0: int, rope_fused: bool) -> None:
+        """Decoder layer i of a prefill on the rows `v`.  rope_fused: RoPE / head split / cache writes in the q|k|v GEMM's epilogue (no
+        fp32 qkv tensor), else the q|k|v GEMM and rope_split_heads as two launches."""
+        d, L = self.dims, self.layers[i]
+        H, I, nh, hd, eps = d.hidden_size, d.intermediate_size, d.num_attention_heads, d.head_dim, d.rms_norm_eps
+        kc, vc, kcl, vcl = self._kv_views(i, v.slot0, v.slot0 + v.nb)
+        ops.rmsnorm_bf16(v.h, L.ln1, eps, v.x16, v.x16_lo)
+        if rope_fused:
+            ops.gemm16_fragw_rope_qkv(v.x16, v.x16_lo, L.wqkv_rope, H, v.nb, s, nh, pos0, self.cos, self.sin, v.q, kc, vc, v.q_lo, kcl, vcl)
+        else:
+            ops.gemm16(v.x16, v.x16_lo, L.wqkv, None, 3 * H, ops.EPI_F32, c=v.qkv)
+            ops.rope_split_heads(v.qkv, v.nb, s, nh, hd, pos0, self.cos, self.sin, v.q, kc, vc, v.q_lo, kcl, vcl)
+        ops.attn_prefill(v.q, kc, vc, v.nb, s, nh, hd, pos0, v.att, v.q_lo, kcl, vcl, v.att_lo)
+        ops.gemm16(v.att, v.att_lo, L.wo, None, H, ops.EPI_RESID, c=v.h, resid=v.h)
+        ops.rmsnorm_bf16(v.h, L.ln2, eps, v.x16, v.x16_lo)
+        ops.gemm16(v.x16, v.x16_lo, L.wgu, None, 2 * I, self._epi_swiglu(), out_hi=v.act, out_lo=v.act_lo)
+        ops.gemm16(v.act, v.act_lo, L.wdown, None, H, ops.EPI_RESID, c=v.h, resid=v.h)
+
+    def _prefill_layers(self, ws, batch: int, s: int, pos0: int, n_layers: int, hidden_sink, slot0: int) -> None:
+        """The decoder layers of a prefill (s > 1): one stream over the whole batch, or two half-batches on two streams."""
+        rope_fused = self._prefill_rope_fused(batch, s)
+        if rope_fused:
+            rope_fused = all(self._rope_weight(self.layers[i]) is not None for i in range(n_layers))
+        if (self.prefill_streams == 2 and rope_fused and batch >= 2 and batch % 2 == 0 and self._prefill_rope_fused(batch // 2, s)
+                and hidden_sink is None and not torch.cuda.is_current_stream_capturing()):
+            self._prefill_two_streams(ws, batch, s, pos0, n_layers, slot0)
+            return
+        v = self._rows(ws, 0, batch, s, slot0)
+        for i in range(n_layers):
+            if hidden_sink is not None:                       # HF output_hidden_states: the stream as it ENTERS every layer
+                hidden_sink.append(v.h.view(batch, s, self.dims.hidden_size).clone())
+            self._prefill_layer(i, v, s, pos0, rope_fused)
 
     def _prefill_two_streams(self, ws, batch: int, s: int, pos0: int, n_layers: int, slot0: int = 0) -> None:
-        """The layer stack of a prefill as two half-batches, each on its own stream, enqueued layer by layer in alternation.
+        """The layer stack of a fused-RoPE prefill as two half-batches, each on its own stream, enqueued layer by layer in alternation.
         The side streams work on row slices of `ws`, tensors allocated on the CALLER's stream: safe only because the workspace is
         persistent (owned by the engine, never returned to the caching allocator while a forward is in flight) and both side streams
         are joined into the caller's stream before this returns."""
@@ -487,26 +534,15 @@ class HipLlamaEngine:
             self._side_streams = (torch.cuda.Stream(device=self.device), torch.cuda.Stream(device=self.device))
         cur = torch.cuda.current_stream()
         half = batch // 2
-        parts = ((0, half), (half, batch))
+        parts = (self._rows(ws, 0, half, s, slot0), self._rows(ws, half, batch, s, slot0))
         for st in self._side_streams:
             st.wait_stream(cur)
         for i in range(n_layers):
-            L = self.layers[i]
-            for st, (b0, b1) in zip(self._side_streams, parts):
+            for st, v in zip(self._side_streams, parts):
                 with torch.cuda.stream(st):
-                    self._prefill_layer_rows(ws, L, i, b0, b1, s, pos0, slot0)
+                    self._prefill_layer(i, v, s, pos0, True)
         for st in self._side_streams:
             cur.wait_stream(st)
-
-    def _decode_body(self, st) -> None:
-        """One decode step on static buffers: ids -> logits, new K/V written at *pos."""
-        d = self.dims
-        B = st["ids"].shape[0]
-        ws = st["ws"]
-        ops.embed_gather(st["ids"].view(-1), self.embed, ws["h"])
-        if not self._layers_forward(ws, B, 1, 0, None, pos_dev=st["pos"]):
-            ops.rmsnorm_bf16(ws["h"], self.norm, d.rms_norm_eps, ws["x16"], ws["x16_lo"])
-        ops.gemm16(ws["x16"], ws["x16_lo"], self.lm_head, None, d.vocab_size, ops.EPI_F32, c=st["logits"])
 
     def _decode_step_graph(self, input_ids: torch.Tensor, pos0: int) -> torch.Tensor:
         """Greedy-decode step as ONE hipGraph replay (opt-in: `decode_graph` / LLARK_DECODE_GRAPH=1).  Bit-identical
@@ -590,13 +626,7 @@ class HipLlamaEngine:
             return self._decode_step_graph(input_ids, pos0)
         ws = self._workspace(B, S)
         h = ws["h"]
-        ops.embed_gather(input_ids.reshape(-1).contiguous(), self.embed, h)
-        for (b, start, frames) in audio_segments:
-            assert self.proj_w is not None, "mm_projector weights not loaded"
-            F = frames.shape[0]
-            a16, a16_lo = ops.split16(frames.contiguous(), torch.bfloat16, want_lo=self.split)
-            r0 = b * S + start + 1
-            ops.gemm16(a16, a16_lo, self.proj_w, self.proj_b, d.hidden_size, ops.EPI_F32, c=h[r0: r0 + F])
+        embed_splice(input_ids, self.embed, h, audio_segments, self.proj_w, self.proj_b, self.split)
         normed = self._layers_forward(ws, B, S, pos0, num_layers, hidden_sink=hidden_sink)
         self.cur_len = pos0 + S
         if hidden_sink is not None:
@@ -609,20 +639,9 @@ class HipLlamaEngine:
         if return_hidden:
             return h.view(B, S, d.hidden_size)
         if last_only and S > 1:
-            hl = h.view(B, S, d.hidden_size)[:, -1].contiguous()
-            x16 = torch.empty((B, d.hidden_size), dtype=torch.bfloat16, device=self.device)
-            x16_lo = torch.empty_like(x16) if self.split else None
-            ops.rmsnorm_bf16(hl, self.norm, d.rms_norm_eps, x16, x16_lo)
-            logits = torch.empty((B, d.vocab_size), dtype=torch.float32, device=self.device)
-            ops.gemm16(x16, x16_lo, self.lm_head, None, d.vocab_size, ops.EPI_F32, c=logits)
-            return logits.view(B, 1, d.vocab_size)
+            return self._head_rows(h.view(B, S, d.hidden_size)[:, -1].contiguous()).view(B, 1, d.vocab_size)
         logits = torch.empty((B * S, d.vocab_size), dtype=torch.float32, device=self.device)
-        if S == 1 and B <= 16 and not normed and (self.fuse_decode_norm_a == "1" or (self.fuse_decode_norm_a == "auto" and ops.gemv_dma_rmsnorm_takes(B, d.vocab_size, d.hidden_size))):
-            ops.gemm16_rmsnorm_a(h, self.norm, d.rms_norm_eps, self.lm_head, d.vocab_size, ops.EPI_F32, self.split, c=logits)
-            return logits.view(B, S, d.vocab_size)
-        if not normed:
-            ops.rmsnorm_bf16(h, self.norm, d.rms_norm_eps, ws["x16"], ws["x16_lo"])
-        ops.gemm16(ws["x16"], ws["x16_lo"], self.lm_head, None, d.vocab_size, ops.EPI_F32, c=logits)
+        self._head(ws, logits, normed, may_fuse=S == 1 and B <= 16)
         return logits.view(B, S, d.vocab_size)
 
     # ---- ragged mode: batch slots with their own cache lengths ---------------------------------------------------------
@@ -705,25 +724,11 @@ class HipLlamaEngine:
 
     def _prefill_run(self, ids: torch.Tensor, segs, slot0: int, last: torch.Tensor) -> torch.Tensor:
         """forward_tokens(last_only=True) of a right-padded batch into cache slots slot0 .., logits of the rows of h listed in `last`."""
-        d = self.dims
         B, S = ids.shape
         ws = self._workspace(B, S)
-        h = ws["h"]
-        ops.embed_gather(ids.reshape(-1), self.embed, h)
-        for (b, start, frames) in segs:
-            assert self.proj_w is not None, "mm_projector weights not loaded"
-            F = frames.shape[0]
-            a16, a16_lo = ops.split16(frames.to(device=self.device, dtype=torch.float32).contiguous(), torch.bfloat16, want_lo=self.split)
-            r0 = b * S + start + 1
-            ops.gemm16(a16, a16_lo, self.proj_w, self.proj_b, d.hidden_size, ops.EPI_F32, c=h[r0: r0 + F])
+        embed_splice(ids, self.embed, ws["h"], segs, self.proj_w, self.proj_b, self.split)
         self._layers_forward(ws, B, S, 0, slot0=slot0)
-        hl = h.index_select(0, last)
-        x16 = torch.empty((B, d.hidden_size), dtype=torch.bfloat16, device=self.device)
-        x16_lo = torch.empty_like(x16) if self.split else None
-        ops.rmsnorm_bf16(hl, self.norm, d.rms_norm_eps, x16, x16_lo)
-        logits = torch.empty((B, d.vocab_size), dtype=torch.float32, device=self.device)
-        ops.gemm16(x16, x16_lo, self.lm_head, None, d.vocab_size, ops.EPI_F32, c=logits)
-        return logits
+        return self._head_rows(ws["h"].index_select(0, last))
 
     def _slot_workspace(self):
         """The decode step's own buffers: a refill prefill (other shapes) does not reallocate them."""
@@ -760,7 +765,6 @@ class HipLlamaEngine:
         token of each slot at position slot_len; idle rows pass through the row-independent GEMMs harmlessly).  sample: optional
         callable logits -> int64 [n_slots] tokens (sampling); greedy otherwise.  Returns (next ids on the device, their host copy,
         the step's fp32 logits [n_slots, V] -- a buffer the next step overwrites)."""
-        d = self.dims
         n = self.n_slots
         if n == 0:
             raise RuntimeError("ragged mode is not active: call init_slots(n) first")
@@ -773,11 +777,6 @@ class HipLlamaEngine:
         h, logits = ws["h"], ws["logits"]
         ops.embed_gather(ids.contiguous(), self.embed, h)
         normed = self._layers_forward(ws, n, 1, 0, pos_rows=self.slot_len)
-        if not normed and (self.fuse_decode_norm_a == "1" or (self.fuse_decode_norm_a == "auto" and ops.gemv_dma_rmsnorm_takes(n, d.vocab_size, d.hidden_size))):
-            ops.gemm16_rmsnorm_a(h, self.norm, d.rms_norm_eps, self.lm_head, d.vocab_size, ops.EPI_F32, self.split, c=logits)
-        else:
-            if not normed:
-                ops.rmsnorm_bf16(h, self.norm, d.rms_norm_eps, ws["x16"], ws["x16_lo"])
-            ops.gemm16(ws["x16"], ws["x16_lo"], self.lm_head, None, d.vocab_size, ops.EPI_F32, c=logits)
+        self._head(ws, logits, normed, may_fuse=True)
         nxt, host = self.advance_slots(logits, eos, pad, out_col, None if sample is None else sample(logits))
         return nxt, host, logits

@@ -21,6 +21,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from .. import ops
+from .engine import embed_splice
 
 
 @dataclass
@@ -155,13 +156,7 @@ class HipMptEngine:
         ws = self._workspace(B, S)
         h, D, E, nh = ws["h"], d.d_model, d.expansion_ratio * d.d_model, d.n_heads
         sp = self.split
-        ops.embed_gather(input_ids.reshape(-1).contiguous(), self.wte, h)
-        for (b, start, frames) in audio_segments:
-            assert self.proj_w is not None, "mm_projector weights not loaded"
-            F = frames.shape[0]
-            a16, a16_lo = ops.split16(frames.contiguous(), torch.bfloat16, want_lo=sp)
-            r0 = b * S + start + 1
-            ops.gemm16(a16, a16_lo, self.proj_w, self.proj_b, D, ops.EPI_F32, c=h[r0: r0 + F])
+        embed_splice(input_ids, self.wte, h, audio_segments, self.proj_w, self.proj_b, sp)
         n_layers = d.n_layers if num_layers is None else num_layers
         for i in range(n_layers):
             Bk = self.blocks[i]
