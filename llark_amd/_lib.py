@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 import subprocess
 from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_uint, c_void_p
 
@@ -37,137 +38,62 @@ def build(force: bool = False, verbose: bool = False) -> str:
     return LIB_PATH
 
 
-# name -> argtypes (all return int unless noted)
-_P = c_void_p
-_SIGS = {
-    "llark_version": [],
-    "llark_device_info": [c_int, c_char_p, c_int],
-    "llark_resample_sinc_host": [_P, c_int64, c_double, _P, _P, c_int, c_int, _P, c_int64],
-    "llark_flac_info_host": [_P, c_int64, _P, _P, _P, _P],
-    "llark_flac_decode_host": [_P, c_int64, _P, c_int64, _P, c_int],
-    "llark_pack_conv_weight": [_P, _P, c_int, c_int, c_int, _P],
-    "llark_conv1d_f32": [_P, c_int, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P],
-    "llark_resblock_f32": [_P, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P],
-    "llark_codebook_norms_f32": [_P, c_int, c_int, _P, _P],
-    "llark_codebook_argmin": [_P, c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P],
-    "llark_prior_embed": [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P],
-    "llark_layernorm_split_f16": [_P, c_int, c_int, c_int, _P, _P, c_float, _P, _P, c_int, _P],
-    "llark_prior_attn": [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P],
-    "llark_pool_window": [_P, c_int, c_int, c_int, c_int, _P, c_int, _P],
-    "llark_pool_mean": [_P, c_int, c_int, c_int, _P, _P, _P],
-    "llark_zero_pad16": [_P, c_int, c_int, c_int, _P],
-    "llark_vqvae_plan_add_conv": [_P, _P, _P, c_int, c_int, c_int, c_int, c_int],
-    "llark_vqvae_plan_add_resblock": [_P, _P, _P, _P, _P, c_int, c_int],
-    "llark_vqvae_encode": [_P, _P, c_int, c_int, _P, _P, c_int64, _P, _P, c_int, _P, _P, _P],
-    "llark_codebook_argmin_tie": [_P, c_int, c_int, c_int, _P, _P, c_int, _P, c_float, c_float, _P, _P, c_int, _P],
-    "llark_vqvae_fix_near_ties": [_P, _P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_int64, _P, _P, c_int, _P, _P],
-    "llark_vqvae_stage_f16x2": [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "llark_vqvae_pack_frag16": [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P],
-    "llark_gemm16": [c_int, c_int, c_int, _P, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_int, _P, c_int,
-                     _P, _P, c_int, _P],
-    "llark_gemm16_ex": [c_int, c_int, c_int, c_int, _P, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_int, _P, c_int,
-                        _P, _P, c_int, _P],
-    "llark_gemm16_ws": [c_int, c_int, c_int, c_int, _P, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_int, _P, c_int,
-                        _P, _P, c_int, _P, _P],
-    "llark_gemm16_lo8": [c_int, _P, _P, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int,
-                         _P, _P, c_int, c_int, _P, _P],
-    "llark_pack_weight_lo8": [_P, c_int, c_int, c_int, c_int, _P, c_int, _P],
-    "llark_gemm16_ln_takes": [c_int, c_int, c_int],
-    "llark_gemm16_ln": [c_int, c_int, _P, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, _P],
-    "llark_ln_stats_finalize": [_P, c_int, c_int, c_int, c_float, _P, _P],
-    "llark_gemm16_fragw_whole_tiles": [c_int, c_int, c_int, c_int, c_int],
-    "llark_gemm16_ln_p": [c_int, c_int, _P, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, _P, _P],
-    "llark_gemm16_lnp_fragw": [c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P, c_int, _P, _P, _P, _P],
-    "llark_ln_stats_finalize_p": [_P, c_int, c_int, c_int, c_float, _P, _P, _P],
-    "llark_ln_row_pred": [_P, c_int, c_int, c_int, c_float, _P, _P],
-    "llark_workspace_destroy": [_P],
-    "llark_layernorm_split_lo8": [_P, c_int, c_int, c_int, _P, _P, c_float, _P, c_int, _P, c_int, c_int, _P],
-    "llark_prior_attn_lo8": [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, c_int, _P],
-    "llark_pack_weight16_frag": [_P, c_int, c_int, c_int, _P, _P],
-    "llark_gemm16_fragw": [c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P, c_int, _P, c_int,
-                           _P, _P, c_int, _P],
-    "llark_gemm16_fragw_sk": [c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P, c_int, _P, c_int,
-                              _P, _P, c_int, _P, c_int64, _P],
-    "llark_gemm16_fragw_rope_qkv": [_P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P, _P, _P, _P, c_int, _P],
-    "llark_gemm16_resid_rmsnorm": [c_int, c_int, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_float, _P, _P,
-                                   c_int, _P],
-    "llark_gemm16_rmsnorm_a": [c_int, c_int, c_int, _P, c_int, _P, c_float, _P, c_int, _P, c_int, c_int, c_int, _P, c_int, _P, _P,
-                               c_int, _P],
-    "llark_gemm16_batched": [c_int, c_int, c_int, _P, _P, c_int, c_int64, _P, c_int, c_int64, c_int, c_int, c_int, _P, c_int,
-                             c_int64, _P, _P, c_int, c_int64, c_int, _P],
-    "llark_pack_weight16": [_P, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P],
-    "llark_split16": [c_int, _P, c_int, c_int, c_int, _P, _P, c_int, _P],
-    "llark_embed_gather": [_P, c_int, _P, c_int, c_int, c_int, _P, c_int, _P],
-    "llark_rmsnorm_bf16": [_P, c_int, c_int, c_int, _P, c_float, _P, _P, c_int, _P],
-    "llark_attn_prefill_bf16_alibi": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P],
-    "llark_attn_decode_bf16_alibi": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P],
-    "llark_gemv16_dma": [c_int, c_int, _P, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P, c_int, _P],
-    "llark_gemv16_dma_rmsnorm": [c_int, c_int, _P, c_int, _P, c_float, _P, c_int, _P, c_int, c_int, c_int, _P, c_int, _P, _P, c_int, _P],
-    "llark_gemm16_t": [c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, _P],
-    "llark_gemm16_t_ex": [c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P],
-    "llark_gemm16_t_sumsq": [c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P],
-    "llark_attn_prefill_bf16_lse": [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P],
-    "llark_attn_backward_bf16": [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P],
-    "llark_layernorm_bf16": [_P, c_int, c_int, c_int, _P, _P, c_float, _P, _P, c_int, _P],
-    "llark_layernorm_f32": [_P, c_int, c_int, c_int, _P, _P, c_float, _P, c_int, _P],
-    "llark_clamp_f32": [_P, c_int64, c_float, _P],
-    "llark_clamp_bwd_bf16": [_P, c_int64, c_float, _P, _P],
-    "llark_sumsq_f32": [_P, c_int64, _P, c_int, _P],
-    "llark_scale_f32": [_P, c_int64, c_float, _P],
-    "llark_gelu_split_bf16": [_P, c_int, c_int, c_int, _P, _P, c_int, _P],
-    "llark_layernorm_bwd": [_P, c_int, _P, _P, c_int, c_int, c_int, c_float, _P, c_int, _P, _P, c_int, _P],
-    "llark_gelu_bwd": [_P, _P, c_int64, _P, _P, _P],
-    "llark_causal_softmax_rows_alibi": [_P, c_int, c_int, c_float, _P, c_int, _P, c_int, _P],
-    "llark_clap_logmel": [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P],
-    "llark_clap_patchify": [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int, _P, _P, c_int, _P],
-    "llark_clap_window_attn": [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P],
-    "llark_layernorm_bf16_dup": [_P, c_int, c_int, c_int, _P, _P, c_float, _P, _P, _P, c_int, _P],
-    "llark_gemm16_act": [c_int, c_int, c_int, c_int, _P, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, _P],
-    "llark_clap_patch_merge": [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P],
-    "llark_mean_rows_f32": [_P, c_int, c_int, c_int, c_int, _P, c_int, _P],
-    "llark_relu_split_bf16": [_P, c_int, c_int, c_int, _P, _P, c_int, _P],
-    "llark_l2_normalize_rows": [_P, c_int, c_int, c_int, c_float, _P],
-    "llark_attn_decode_rope_bf16": [_P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P, _P, c_int, _P, _P, _P, _P],
-    "llark_attn_decode_rope_bf16_rows": [_P, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P, _P, c_int, _P, _P, _P, _P],
-    "llark_decode_advance_rows": [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int64, c_int64, _P],
-    "llark_rope_split_heads_dpos": [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P],
-    "llark_attn_decode_bf16_dpos": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, _P, _P, _P],
-    "llark_rope_split_heads": [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P, _P, _P, _P, c_int, _P],
-    "llark_attn_prefill_bf16": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P],
-    "llark_attn_decode_bf16": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P],
-    "llark_cross_entropy_shifted": [_P, c_int, c_int, c_int, c_int, _P, c_int64, _P, _P, _P],
-    "llark_transpose16": [_P, c_int, c_int, c_int, _P, c_int, c_int, c_int64, c_int64, _P],
-    "llark_split_heads16": [_P, c_int, c_int, c_int, c_int, _P, _P],
-    "llark_causal_softmax_rows": [_P, c_int, c_int, c_float, _P, c_int, _P],
-    "llark_attn_ds": [_P, _P, c_int, c_int, c_float, _P, c_int, _P],
-    "llark_rope_merge_bwd": [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P],
-    "llark_rmsnorm_bwd": [_P, _P, _P, c_int, c_int, c_float, _P, c_int, _P, _P],
-    "llark_rmsnorm_bwd_out16": [_P, _P, _P, c_int, c_int, c_float, _P, c_int, _P, _P, c_int, _P],
-    "llark_swiglu_fwd": [_P, c_int, c_int, _P, _P],
-    "llark_swiglu_bwd": [_P, _P, c_int, c_int, _P, _P],
-    "llark_cross_entropy_bwd": [_P, c_int, c_int, c_int, c_int, _P, _P, _P, c_float, _P, c_int, _P],
-    "llark_colsum_f32": [_P, c_int, c_int, c_int, _P, _P],
-    "llark_gather_rows_f32": [_P, c_int, _P, c_int, c_int, _P, c_int, _P],
-    "llark_scatter_add_rows_f32": [_P, c_int, _P, c_int, c_int, _P, c_int, _P],
-    "llark_adamw": [c_int, _P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_float, _P],
-    "llark_adamw_clip": [c_int, _P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_float, _P, c_float, _P],
-    "llark_gemm16_fragw_swiglu_train": [c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P],
-    "llark_pack_frag_t16": [_P, c_int, c_int, c_int, _P, _P],
-    "llark_gemm16_ta_fragw": [c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P],
-    "llark_pack_frag_t16x16": [_P, c_int, c_int, c_int, _P, _P],
-    "llark_gemm16_ta_fragw16": [c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P],
-    "llark_gemm16_fragw_rope_qkv_train": [_P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P, c_int, _P, _P],
-    "llark_attn_backward_bf16_fused": [_P, _P, _P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, c_int, _P, _P],
-    "llark_gemv16_dma_blocks": [c_int, c_int],
-    "llark_gemv16_dma_chain": [c_int, c_int, _P, _P, c_int, _P, c_int, _P, c_float, _P, c_int, _P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P, c_int, _P, c_uint, _P, _P],
-    "llark_attn_decode_rope_bf16_chain": [_P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P],
-    "llark_adamw_twins": [_P, _P, _P, _P, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, c_float, _P, c_float, _P, c_int, _P, _P],
-}
+# ---- the C ABI, read from include/llark_hip.h: the header is the only place a signature is written down ----------------
+HEADER = os.path.join(_HERE, "..", "include", "llark_hip.h")
+_CTYPES = {"int": c_int, "int64_t": c_int64, "long long": c_int64, "unsigned": c_uint, "float": c_float, "double": c_double,
+           "llark_stream_t": c_void_p, "llark_workspace_t": c_void_p}
+_PROTO = re.compile(r"(?:\A|(?<=[;{}]))\s*([\w\s*]+?)\s*\b(llark_\w+)\s*\(([^()]*)\)\s*;")
+
+
+def _ctype(decl: str, proto: str, param: bool):
+    """ctypes type of one parameter declaration (``param``) or of a return type; an unknown type raises."""
+    tok = re.findall(r"\w+|\*|\[\s*\]", re.sub(r"\bconst\b", " ", decl))
+    if param:                                   # drop the parameter's name; `T x[]` is `T* x`
+        tok = tok[:-2] + ["*"] if tok and tok[-1][0] == "[" else tok[:-1]
+    if "*" in tok:
+        return c_char_p if tok[0] == "char" else c_void_p
+    if tok == ["void"] and not param:
+        return None
+    if " ".join(tok) not in _CTYPES:
+        raise LlarkHipError(f"include/llark_hip.h: unknown type in '{decl.strip()}' of `{proto}`")
+    return _CTYPES[" ".join(tok)]
+
+
+def parse_header(text: str) -> dict:
+    """name -> (restype, argtypes, index of the llark_stream_t parameter or None) for every ``ret llark_name(params);`` of a C
+    header.  Fails loudly: an unknown type, or a ``llark_name(`` the prototype pattern did not take, raises LlarkHipError."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    protos = {}
+    for m in _PROTO.finditer(text):
+        ret, name, params = m.groups()
+        proto = " ".join(m.group(0).split())
+        decls = [] if params.strip() in ("", "void") else params.split(",")
+        stream = [i for i, d in enumerate(decls) if re.search(r"\bllark_stream_t\b", d)]
+        protos[name] = (_ctype(ret, proto, False), [_ctype(d, proto, True) for d in decls], stream[0] if stream else None)
+    mentioned = re.findall(r"\b(llark_\w+)\s*\(", text)
+    if len(protos) != len(mentioned):
+        raise LlarkHipError(f"include/llark_hip.h: {len(mentioned)} `llark_name(` but {len(protos)} prototypes parsed "
+                            f"(not taken: {sorted(set(mentioned) - set(protos))})")
+    return protos
+
+
+def _read_header() -> str:
+    try:
+        with open(HEADER) as f:
+            return f.read()
+    except OSError as e:                        # no fallback table: without the header there are no signatures
+        raise LlarkHipError(f"cannot read {HEADER}: {e}") from e
+
+
+_PROTOS = parse_header(_read_header())
+_SIGS = {name: p[1] for name, p in _PROTOS.items()}            # name -> argtypes
+_STREAM_ARG = {name: p[2] for name, p in _PROTOS.items()}      # name -> position of the llark_stream_t parameter, or None
 
 
 def declared_symbols():
-    """Every symbol ``include/llark_hip.h`` declares (kept in sync by tests/test_abi.py)."""
-    return sorted(list(_SIGS.keys()) + ["llark_last_error", "llark_vqvae_plan_create", "llark_vqvae_plan_destroy", "llark_workspace_create", "llark_gemm16_sk_scratch_bytes"])
+    """Every symbol ``include/llark_hip.h`` declares."""
+    return sorted(_PROTOS)
 
 
 # ---- host-side launch lists -------------------------------------------------------------------------------------------
@@ -218,20 +144,10 @@ def _real_lib():
             L = ctypes.CDLL(LIB_PATH)
         except OSError as e:  # fail loudly: there is no fallback path
             raise LlarkHipError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, args in _SIGS.items():
+        for name, (restype, argtypes, _) in _PROTOS.items():
             fn = getattr(L, name)
-            fn.argtypes = args
-            fn.restype = c_int
-        L.llark_last_error.argtypes = []
-        L.llark_last_error.restype = c_char_p
-        L.llark_vqvae_plan_create.argtypes = []
-        L.llark_vqvae_plan_create.restype = c_void_p
-        L.llark_vqvae_plan_destroy.argtypes = [c_void_p]
-        L.llark_vqvae_plan_destroy.restype = None
-        L.llark_workspace_create.argtypes = []
-        L.llark_workspace_create.restype = c_void_p
-        L.llark_gemm16_sk_scratch_bytes.argtypes = []
-        L.llark_gemm16_sk_scratch_bytes.restype = c_int64
+            fn.argtypes = argtypes
+            fn.restype = restype
         _lib = L
     return _lib
 

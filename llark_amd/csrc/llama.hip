@@ -604,17 +604,17 @@ static void launch_attn_prefill(hipStream_t st, const bf16_t* q, const bf16_t* k
     auto pairs_ok = [&](int nt) { const long wgs = (long)((nt + 1) / 2) * nbh; return nt >= 2 && (wgs >= 2048 || wgs == 512 || wgs == 1024); };
     auto go = [&](auto alibi_c) {
         constexpr bool AL = decltype(alibi_c)::value;
-        if (!SPLIT && (long)cdiv(s, 128) * nbh >= 1024) {          // (hi+lo planes: two query sets per wave do not fit 256 registers)
-            const int nt = cdiv(s, 128), pr = pairs_ok(nt);
-            (void)hipFuncSetAttribute((const void*)attn_prefill_kernel<SPLIT, SPLIT ? 1 : 2, P2, AL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            attn_prefill_kernel<SPLIT, SPLIT ? 1 : 2, P2, AL><<<(pr ? (nt + 1) / 2 : nt) * nbh, 256, lds, st>>>(q, kc, vtc, q_lo, kc_lo, vtc_lo, out, out_lo, s, nh, nbh,
-                                                                                                      past, smax, scale, alibi, lse, pr);
-        } else {
-            const int nt = cdiv(s, 64), pr = pairs_ok(nt);
-            (void)hipFuncSetAttribute((const void*)attn_prefill_kernel<SPLIT, 1, P2, AL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            attn_prefill_kernel<SPLIT, 1, P2, AL><<<(pr ? (nt + 1) / 2 : nt) * nbh, 256, lds, st>>>(q, kc, vtc, q_lo, kc_lo, vtc_lo, out, out_lo, s, nh, nbh,
-                                                                                          past, smax, scale, alibi, lse, pr);
-        }
+        auto run = [&](auto nq_c) {                                 // NQ query sets of 64 per workgroup
+            constexpr int NQ = decltype(nq_c)::value;
+            const int nt = cdiv(s, 64 * NQ), pr = pairs_ok(nt);
+            static PerDeviceOnce once;                              // per (instantiation, device): the attribute belongs to the device's function object
+            if (once.first()) (void)hipFuncSetAttribute((const void*)attn_prefill_kernel<SPLIT, NQ, P2, AL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            attn_prefill_kernel<SPLIT, NQ, P2, AL><<<(pr ? (nt + 1) / 2 : nt) * nbh, 256, lds, st>>>(q, kc, vtc, q_lo, kc_lo, vtc_lo, out, out_lo, s, nh, nbh, past,
+                                                                                           smax, scale, alibi, lse, pr);
+        };
+        // (hi+lo planes: two query sets per wave do not fit 256 registers)
+        if (!SPLIT && (long)cdiv(s, 128) * nbh >= 1024) run(std::integral_constant<int, SPLIT ? 1 : 2>{});
+        else run(std::integral_constant<int, 1>{});
     };
     if (alibi) go(std::true_type{});
     else go(std::false_type{});
@@ -790,27 +790,62 @@ __global__ __launch_bounds__(NW * 64, (NW >= 16 && UBT == 4) ? 7 : 1) void attn_
     chain_signal(ChainSync{nullptr, 0u, chain_done});                 // round 6: a chained consumer (o_proj) may be waiting for this head
 }
 
-// 16 waves per block while the grid is smaller than the chip, 4 otherwise
-#ifndef ATTN_DECODE_WIDE
-#define ATTN_DECODE_WIDE 0        // 1: 8 loads in flight per lane at 16 waves beyond 256 keys -- measured in round 6 (profiles/r06_decode_attn_ub_ab.txt): no gain (302.9 vs 302.1 ms per clip), off
-#endif
-// `keys`: how many keys the walk may see (the host position + 1, or smax when the position lives in device memory)
-template <bool ROWS = false, typename... Args>
-static void launch_attn_decode(int nh, int batch, size_t lds, hipStream_t s, int keys, bool chained, Args... args) {
-    dim3 grid(nh, batch);
-    if ((long)nh * batch < 256) {
-        if (ATTN_DECODE_WIDE && keys > 256 && !chained) attn_decode_kernel<16, 8, ROWS><<<grid, 1024, lds, s>>>(args...);
-        else attn_decode_kernel<16, 4, ROWS><<<grid, 1024, lds, s>>>(args...);
-    } else attn_decode_kernel<4, 8, ROWS><<<grid, 256, lds, s>>>(args...);
-}
+// Every decode-attention launch goes through attn_decode(): the entry points at the end of this file fill in what they were given (the
+// rest stays zero) and their own name.  16 waves per block while the grid is smaller than the chip, 4 otherwise.
+enum AttnDecodePos { POS_HOST, POS_DEV, POS_ROWS };        // the new token's position: a host int, *pos_dev, pos_rows[batch]
+struct AttnDecodeArgs {
+    const char* name;
+    bool fused;                                            // RoPE + cache append in the kernel (qkv, cos_t, sin_t) or rotated planes (q, q_lo)
+    const void *q, *q_lo;
+    const float *qkv, *cos_t, *sin_t, *alibi;
+    void *k_cache, *vt_cache, *k_cache_lo, *vt_cache_lo, *out, *out_lo;
+    int batch, nh, hd, smax, max_pos;                      // max_pos: rows of cos_t / sin_t
+    AttnDecodePos from;
+    long total;                                            // POS_HOST: keys visible = position of the new token + 1
+    const int *pos_dev, *pos_rows;                         // POS_DEV / POS_ROWS: device memory
+    unsigned* chain_done;
+    llark_stream_t stream;
+};
 
-template <bool ROWS = false>
-static void attn_decode_lds_limit(int lds) {
-    (void)hipFuncSetAttribute((const void*)attn_decode_kernel<4, 8, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)attn_decode_kernel<16, 4, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)attn_decode_kernel<16, 8, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+static int attn_decode(const AttnDecodeArgs& a) {
+    LLARK_REQUIRE(a.k_cache && a.vt_cache && a.out && (a.fused ? a.qkv && a.cos_t && a.sin_t : a.q != nullptr) &&
+                      (a.from == POS_HOST || (a.from == POS_DEV ? a.pos_dev : a.pos_rows)), "%s: null pointer", a.name);
+    LLARK_REQUIRE(a.hd == 128, "%s: head_dim must be 128 (Llama-2), got %d", a.name, a.hd);
+    LLARK_REQUIRE(!a.fused || ((a.k_cache_lo == nullptr) == (a.vt_cache_lo == nullptr) && (a.k_cache_lo == nullptr) == (a.out_lo == nullptr)),
+                  "%s: give all lo planes (fp32-class mode) or none", a.name);
+    bool ok = a.batch > 0 && a.nh > 0 && (!a.fused || a.smax % 8 == 0);
+    if (a.from == POS_HOST) ok = ok && a.total > 0 && a.total <= a.smax && (!a.fused || a.total <= a.max_pos);
+    if (a.from == POS_DEV) ok = ok && (a.fused || a.smax > 0);
+    if (a.from == POS_ROWS) ok = ok && a.smax > 0 && a.smax <= a.max_pos;
+    LLARK_REQUIRE(ok, "%s: bad shape batch=%d nh=%d pos=%ld smax=%d max_pos=%d", a.name, a.batch, a.nh, a.total - 1, a.smax, a.max_pos);
+    // dynamic LDS holds the scores: the keys a host position makes visible, else the longest context the cache can hold
+    const size_t lds = (a.from == POS_HOST ? (size_t)((a.total + 7) & ~7L) : (size_t)a.smax) * sizeof(float);
+    LLARK_REQUIRE(lds <= 128 * 1024, "%s: context too long for the LDS score buffer (total=%ld smax=%d)", a.name, a.total, a.smax);
+    const float scale = (float)(1.0 / sqrt((double)a.hd));
+    const int total = a.from == POS_HOST ? (int)a.total : 1;
+    auto go = [&](auto rows_c) {
+        constexpr bool ROWS = decltype(rows_c)::value;
+        auto launch = [&](auto kern, int threads) {
+            kern<<<dim3(a.nh, a.batch), threads, lds, (hipStream_t)a.stream>>>(
+                (const bf16_t*)a.q, (bf16_t*)a.k_cache, (bf16_t*)a.vt_cache, (const bf16_t*)a.q_lo, (bf16_t*)a.k_cache_lo, (bf16_t*)a.vt_cache_lo,
+                (bf16_t*)a.out, (bf16_t*)a.out_lo, a.nh, total, a.smax, scale, ROWS ? a.pos_rows : a.pos_dev, a.alibi, a.qkv, a.cos_t, a.sin_t, a.chain_done);
+        };
+        // the dynamic LDS limit is raised per device and kernel family (not a stream op: outside any capture, by the first eager call
+        // that needs it); slot() = the size this device has been granted
+        static PerDeviceOnce once;
+        const bool first = once.first();
+        if (lds > 48 * 1024 && (first || (int)lds > once.slot())) {
+            (void)hipFuncSetAttribute((const void*)attn_decode_kernel<4, 8, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            (void)hipFuncSetAttribute((const void*)attn_decode_kernel<16, 4, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            once.slot() = (int)lds;
+        }
+        if ((long)a.nh * a.batch < 256) launch(attn_decode_kernel<16, 4, ROWS>, 1024);
+        else launch(attn_decode_kernel<4, 8, ROWS>, 256);
+    };
+    if (a.from == POS_ROWS) go(std::true_type{});
+    else go(std::false_type{});
+    return check_launch(a.name);
 }
-
 
 // ------------------------------------------------------------------------------------------
 // Shifted cross-entropy (m2t/models/llamav2.py:316-325): row (b,s), s < S-1, predicts labels[b][s+1];
@@ -1054,21 +1089,22 @@ extern "C" int llark_attn_prefill_bf16(const void* q, const void* k_cache, const
                                          out_lo, nullptr, stream);
 }
 
+// Decode attention.  Unfused forms: q already rotated and the caches appended (llark_rope_split_heads[_dpos]); `total` keys visible, or
+// *pos_dev + 1 (one captured hipGraph of the decode step serves every generated token).
+static AttnDecodeArgs attn_decode_args(const char* name, const void* q, const void* k_cache, const void* vt_cache, const void* q_lo, const void* k_cache_lo,
+                                       const void* vt_cache_lo, int batch, int nh, int hd, int smax, void* out, void* out_lo, llark_stream_t stream) {
+    AttnDecodeArgs a = {};
+    a.name = name, a.q = q, a.q_lo = q_lo, a.k_cache = (void*)k_cache, a.vt_cache = (void*)vt_cache, a.k_cache_lo = (void*)k_cache_lo;
+    a.vt_cache_lo = (void*)vt_cache_lo, a.batch = batch, a.nh = nh, a.hd = hd, a.smax = smax, a.out = out, a.out_lo = out_lo, a.stream = stream;
+    return a;
+}
+
 extern "C" int llark_attn_decode_bf16_alibi(const void* q, const void* k_cache, const void* vt_cache, const void* q_lo,
                                             const void* k_cache_lo, const void* vt_cache_lo, int batch, int nh, int hd, int total,
                                             int smax, void* out, void* out_lo, const float* alibi_slopes, llark_stream_t stream) {
-    LLARK_REQUIRE(q && k_cache && vt_cache && out, "attn_decode: null pointer");
-    LLARK_REQUIRE(hd == 128, "attn_decode: head_dim must be 128 (Llama-2), got %d", hd);
-    LLARK_REQUIRE(batch > 0 && nh > 0 && total > 0 && total <= smax, "attn_decode: bad shape total=%d smax=%d", total, smax);
-    const float scale = (float)(1.0 / sqrt((double)hd));
-    const size_t lds = (size_t)((total + 7) & ~7) * sizeof(float);
-    LLARK_REQUIRE(lds <= 128 * 1024, "attn_decode: context %d too long for the LDS score buffer", total);
-    if (lds > 48 * 1024) attn_decode_lds_limit((int)lds);
-    launch_attn_decode(nh, batch, lds, (hipStream_t)stream, total, false, (const bf16_t*)q, (bf16_t*)k_cache, (bf16_t*)vt_cache,
-                       (const bf16_t*)q_lo, (bf16_t*)k_cache_lo, (bf16_t*)vt_cache_lo, (bf16_t*)out, (bf16_t*)out_lo, nh,
-                       total, smax, scale, (const int*)nullptr, alibi_slopes, (const float*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr, (unsigned*)nullptr);
-    return check_launch("attn_decode");
+    AttnDecodeArgs a = attn_decode_args("attn_decode", q, k_cache, vt_cache, q_lo, k_cache_lo, vt_cache_lo, batch, nh, hd, smax, out, out_lo, stream);
+    a.from = POS_HOST, a.total = total, a.alibi = alibi_slopes;
+    return attn_decode(a);
 }
 
 extern "C" int llark_attn_decode_bf16(const void* q, const void* k_cache, const void* vt_cache, const void* q_lo,
@@ -1081,57 +1117,32 @@ extern "C" int llark_attn_decode_bf16(const void* q, const void* k_cache, const 
 extern "C" int llark_attn_decode_bf16_dpos(const void* q, const void* k_cache, const void* vt_cache, const void* q_lo,
                                            const void* k_cache_lo, const void* vt_cache_lo, int batch, int nh, int hd,
                                            const int* pos_dev, int smax, void* out, void* out_lo, llark_stream_t stream) {
-    LLARK_REQUIRE(q && k_cache && vt_cache && out && pos_dev, "attn_decode_dpos: null pointer");
-    LLARK_REQUIRE(hd == 128, "attn_decode_dpos: head_dim must be 128 (Llama-2), got %d", hd);
-    LLARK_REQUIRE(batch > 0 && nh > 0 && smax > 0, "attn_decode_dpos: bad shape");
-    const float scale = (float)(1.0 / sqrt((double)hd));
-    const size_t lds = (size_t)smax * sizeof(float);              // sized for the longest context the cache can hold
-    LLARK_REQUIRE(lds <= 128 * 1024, "attn_decode_dpos: cache length %d too long for the LDS score buffer", smax);
-    static int attr_lds = 0;                                      // not a stream op: raise the limit outside any capture
-    if ((int)lds > 48 * 1024 && (int)lds > attr_lds) {
-        attn_decode_lds_limit((int)lds);
-        attr_lds = (int)lds;
-    }
-    launch_attn_decode(nh, batch, lds, (hipStream_t)stream, smax, false, (const bf16_t*)q, (bf16_t*)k_cache, (bf16_t*)vt_cache,
-                       (const bf16_t*)q_lo, (bf16_t*)k_cache_lo, (bf16_t*)vt_cache_lo, (bf16_t*)out, (bf16_t*)out_lo, nh, 1,
-                       smax, scale, pos_dev, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (unsigned*)nullptr);
-    return check_launch("attn_decode_dpos");
+    AttnDecodeArgs a = attn_decode_args("attn_decode_dpos", q, k_cache, vt_cache, q_lo, k_cache_lo, vt_cache_lo, batch, nh, hd, smax, out, out_lo, stream);
+    a.from = POS_DEV, a.pos_dev = pos_dev;
+    return attn_decode(a);
 }
 
 // Decode step: RoPE of the new token + KV-cache append + attention over the cache in ONE launch per layer (replaces
 // llark_rope_split_heads[_dpos] followed by llark_attn_decode_bf16[_alibi|_dpos]; m2t/models/llamav2.py:339-365 decode loop).
 // qkv fp32 [batch][3 * nh * 128] of the new token; position = pos (host int) or *pos_dev when pos_dev != NULL.
-static int attn_decode_rope_impl(const float* qkv, int batch, int nh, int hd, int pos, const int* pos_dev, const float* cos_t,
-                                 const float* sin_t, int max_pos, void* k_cache, void* vt_cache, void* k_cache_lo,
-                                 void* vt_cache_lo, int smax, void* out, void* out_lo, const float* alibi_slopes, unsigned* chain_done,
-                                 llark_stream_t stream) {
-    LLARK_REQUIRE(qkv && cos_t && sin_t && k_cache && vt_cache && out, "attn_decode_rope: null pointer");
-    LLARK_REQUIRE(hd == 128, "attn_decode_rope: head_dim must be 128 (Llama-2), got %d", hd);
-    LLARK_REQUIRE((k_cache_lo == nullptr) == (vt_cache_lo == nullptr) && (k_cache_lo == nullptr) == (out_lo == nullptr),
-                  "attn_decode_rope: give all lo planes (fp32-class mode) or none");
-    LLARK_REQUIRE(batch > 0 && nh > 0 && smax % 8 == 0 && (pos_dev || (pos >= 0 && pos < smax && pos < max_pos)),
-                  "attn_decode_rope: bad shape batch=%d pos=%d smax=%d max_pos=%d", batch, pos, smax, max_pos);
-    const float scale = (float)(1.0 / sqrt((double)hd));
-    const int total = pos_dev ? 1 : pos + 1;
-    const size_t lds = pos_dev ? (size_t)smax * sizeof(float) : (size_t)((total + 7) & ~7) * sizeof(float);
-    LLARK_REQUIRE(lds <= 128 * 1024, "attn_decode_rope: context too long for the LDS score buffer");
-    static int attr_lds = 0;
-    if ((int)lds > 48 * 1024 && (int)lds > attr_lds) {
-        attn_decode_lds_limit((int)lds);
-        attr_lds = (int)lds;
-    }
-    launch_attn_decode(nh, batch, lds, (hipStream_t)stream, pos_dev ? smax : total, chain_done != nullptr, (const bf16_t*)nullptr, (bf16_t*)k_cache, (bf16_t*)vt_cache,
-                       (const bf16_t*)nullptr, (bf16_t*)k_cache_lo, (bf16_t*)vt_cache_lo, (bf16_t*)out, (bf16_t*)out_lo, nh, total, smax,
-                       scale, pos_dev, alibi_slopes, qkv, cos_t, sin_t, chain_done);
-    return check_launch("attn_decode_rope");
+static AttnDecodeArgs attn_decode_rope_args(const char* name, const float* qkv, int batch, int nh, int hd, const float* cos_t, const float* sin_t,
+                                            int max_pos, void* k_cache, void* vt_cache, void* k_cache_lo, void* vt_cache_lo, int smax, void* out,
+                                            void* out_lo, const float* alibi_slopes, llark_stream_t stream) {
+    AttnDecodeArgs a = {};
+    a.name = name, a.fused = true, a.qkv = qkv, a.cos_t = cos_t, a.sin_t = sin_t, a.max_pos = max_pos, a.alibi = alibi_slopes, a.stream = stream;
+    a.k_cache = k_cache, a.vt_cache = vt_cache, a.k_cache_lo = k_cache_lo, a.vt_cache_lo = vt_cache_lo, a.out = out, a.out_lo = out_lo;
+    a.batch = batch, a.nh = nh, a.hd = hd, a.smax = smax;
+    return a;
 }
 
 extern "C" int llark_attn_decode_rope_bf16(const float* qkv, int batch, int nh, int hd, int pos, const int* pos_dev, const float* cos_t,
                                            const float* sin_t, int max_pos, void* k_cache, void* vt_cache, void* k_cache_lo,
                                            void* vt_cache_lo, int smax, void* out, void* out_lo, const float* alibi_slopes,
                                            llark_stream_t stream) {
-    return attn_decode_rope_impl(qkv, batch, nh, hd, pos, pos_dev, cos_t, sin_t, max_pos, k_cache, vt_cache, k_cache_lo, vt_cache_lo, smax, out,
-                                 out_lo, alibi_slopes, nullptr, stream);
+    AttnDecodeArgs a = attn_decode_rope_args("attn_decode_rope", qkv, batch, nh, hd, cos_t, sin_t, max_pos, k_cache, vt_cache, k_cache_lo,
+                                             vt_cache_lo, smax, out, out_lo, alibi_slopes, stream);
+    a.from = pos_dev ? POS_DEV : POS_HOST, a.total = (long)pos + 1, a.pos_dev = pos_dev;
+    return attn_decode(a);
 }
 
 // ... as the PRODUCER of a chained launch (llark_gemv16_dma_chain): every (batch, head) workgroup adds 1 to *done once its slice of `out` is
@@ -1142,34 +1153,21 @@ extern "C" int llark_attn_decode_rope_bf16_chain(const float* qkv, int batch, in
                                                  void* vt_cache_lo, int smax, void* out, void* out_lo, const float* alibi_slopes,
                                                  unsigned* done, llark_stream_t stream) {
     LLARK_REQUIRE(done, "attn_decode_rope_chain: null counter");
-    return attn_decode_rope_impl(qkv, batch, nh, hd, pos, pos_dev, cos_t, sin_t, max_pos, k_cache, vt_cache, k_cache_lo, vt_cache_lo, smax, out,
-                                 out_lo, alibi_slopes, done, stream);
+    AttnDecodeArgs a = attn_decode_rope_args("attn_decode_rope_chain", qkv, batch, nh, hd, cos_t, sin_t, max_pos, k_cache, vt_cache, k_cache_lo,
+                                             vt_cache_lo, smax, out, out_lo, alibi_slopes, stream);
+    a.from = pos_dev ? POS_DEV : POS_HOST, a.total = (long)pos + 1, a.pos_dev = pos_dev, a.chain_done = done;
+    return attn_decode(a);
 }
 
 // Ragged decode step over batch slots: llark_attn_decode_rope_bf16 with the position of sequence b read from pos_rows[b] (idle slot: < 0).
-// Dynamic LDS is sized for smax keys, as in llark_attn_decode_bf16_dpos; the wave count follows nh * batch (launch_attn_decode).
 extern "C" int llark_attn_decode_rope_bf16_rows(const float* qkv, int batch, int nh, int hd, const int* pos_rows, const float* cos_t,
                                                 const float* sin_t, int max_pos, void* k_cache, void* vt_cache, void* k_cache_lo,
                                                 void* vt_cache_lo, int smax, void* out, void* out_lo, const float* alibi_slopes,
                                                 llark_stream_t stream) {
-    LLARK_REQUIRE(qkv && pos_rows && cos_t && sin_t && k_cache && vt_cache && out, "attn_decode_rope_rows: null pointer");
-    LLARK_REQUIRE(hd == 128, "attn_decode_rope_rows: head_dim must be 128 (Llama-2), got %d", hd);
-    LLARK_REQUIRE((k_cache_lo == nullptr) == (vt_cache_lo == nullptr) && (k_cache_lo == nullptr) == (out_lo == nullptr),
-                  "attn_decode_rope_rows: give all lo planes (fp32-class mode) or none");
-    LLARK_REQUIRE(batch > 0 && nh > 0 && smax > 0 && smax % 8 == 0 && smax <= max_pos,
-                  "attn_decode_rope_rows: bad shape batch=%d smax=%d max_pos=%d", batch, smax, max_pos);
-    const float scale = (float)(1.0 / sqrt((double)hd));
-    const size_t lds = (size_t)smax * sizeof(float);
-    LLARK_REQUIRE(lds <= 128 * 1024, "attn_decode_rope_rows: cache length %d too long for the LDS score buffer", smax);
-    static int attr_lds = 0;
-    if ((int)lds > 48 * 1024 && (int)lds > attr_lds) {
-        attn_decode_lds_limit<true>((int)lds);
-        attr_lds = (int)lds;
-    }
-    launch_attn_decode<true>(nh, batch, lds, (hipStream_t)stream, smax, false, (const bf16_t*)nullptr, (bf16_t*)k_cache, (bf16_t*)vt_cache,
-                             (const bf16_t*)nullptr, (bf16_t*)k_cache_lo, (bf16_t*)vt_cache_lo, (bf16_t*)out, (bf16_t*)out_lo, nh, 1, smax,
-                             scale, pos_rows, alibi_slopes, qkv, cos_t, sin_t, (unsigned*)nullptr);
-    return check_launch("attn_decode_rope_rows");
+    AttnDecodeArgs a = attn_decode_rope_args("attn_decode_rope_rows", qkv, batch, nh, hd, cos_t, sin_t, max_pos, k_cache, vt_cache, k_cache_lo,
+                                             vt_cache_lo, smax, out, out_lo, alibi_slopes, stream);
+    a.from = POS_ROWS, a.pos_rows = pos_rows;
+    return attn_decode(a);
 }
 
 extern "C" int llark_decode_advance_rows(const float* logits, int ldl, int vocab, int batch, const int64_t* choice, int* pos_rows, int* state,

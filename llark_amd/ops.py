@@ -95,8 +95,9 @@ class LaunchList:
         s_now, s_rec = _stream(), self.stream
         timing = _TIMERS is not None
         for fn, name, args, label in self.calls:
-            if args and args[-1] == s_rec and s_now != s_rec:
-                args = args[:-1] + (s_now,)
+            i = _lib._STREAM_ARG[name]              # the parameter the header types as llark_stream_t
+            if i is not None and args[i] == s_rec and s_now != s_rec:
+                args = args[:i] + (s_now,) + args[i + 1:]
             if timing and label is not None:
                 with _timed(label[0], label[1]):
                     rc = fn(*args)
@@ -120,6 +121,14 @@ def _dev(t: torch.Tensor, name: str, dtype=None, contiguous=True) -> int:
     if contiguous and not t.is_contiguous():
         raise ValueError(f"{name}: tensor must be contiguous")
     return t.data_ptr()
+
+
+def _opt(t, name: str, dtype=None, contiguous=True) -> Optional[int]:
+    return None if t is None else _dev(t, name, dtype, contiguous)
+
+
+def _ld(t) -> int:
+    return 0 if t is None else t.stride(0)
 
 
 # Caller-owned workspaces of the persistent GEMM kernels (include/llark_hip.h: llark_workspace_create): one per
@@ -250,13 +259,12 @@ def vqvae_stage(x, n: int, cin: int, tin: int, st: dict, out_planes=None, out_f3
     dil = (ctypes.c_int * len(st["dil"]))(*st["dil"])
     wexp = (ctypes.c_int * len(st["wexp"]))(*st["wexp"])
     assert len(st["wexp"]) == 2 + 2 * len(st["dil"])
-    opt = lambda t, name, dt: _dev(t, name, dt) if t is not None else None      # noqa: E731
     check(_lib.lib().llark_vqvae_stage_f16x2(
-        audio, in_hi, in_lo, n, cin, tin, opt(st["w0f"], "w0f", torch.float32), opt(st["w0_hi"], "w0_hi", torch.float16),
-        opt(st["w0_lo"], "w0_lo", torch.float16), _dev(st["b0"], "b0", torch.float32), _dev(st["wr_hi"], "wr_hi", torch.float16),
+        audio, in_hi, in_lo, n, cin, tin, _opt(st["w0f"], "w0f", torch.float32), _opt(st["w0_hi"], "w0_hi", torch.float16),
+        _opt(st["w0_lo"], "w0_lo", torch.float16), _dev(st["b0"], "b0", torch.float32), _dev(st["wr_hi"], "wr_hi", torch.float16),
         _dev(st["wr_lo"], "wr_lo", torch.float16), _dev(st["br"], "br", torch.float32), len(st["dil"]),
-        ctypes.cast(dil, ctypes.c_void_p), opt(st["wo_hi"], "wo_hi", torch.float16), opt(st["wo_lo"], "wo_lo", torch.float16),
-        opt(st["bo"], "bo", torch.float32), ctypes.cast(wexp, ctypes.c_void_p), out_planes[0].data_ptr() if out_planes is not None else None,
+        ctypes.cast(dil, ctypes.c_void_p), _opt(st["wo_hi"], "wo_hi", torch.float16), _opt(st["wo_lo"], "wo_lo", torch.float16),
+        _opt(st["bo"], "bo", torch.float32), ctypes.cast(wexp, ctypes.c_void_p), out_planes[0].data_ptr() if out_planes is not None else None,
         out_planes[1].data_ptr() if out_planes is not None else None, out_f32.data_ptr() if out_f32 is not None else None, _stream()),
         "vqvae_stage")
 
@@ -383,9 +391,8 @@ def pool_window(h: torch.Tensor, frame_len: int, frames: int) -> torch.Tensor:
 def pool_mean(h: torch.Tensor, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
     n, t, width = h.shape
     out = torch.empty((n, width), dtype=torch.float32, device=h.device)
-    lp = _dev(lens, "lens", torch.int32) if lens is not None else None
-    check(_lib.lib().llark_pool_mean(_dev(h, "h", torch.float32), n, t, width, lp, _dev(out, "out"), _stream()),
-          "pool_mean")
+    check(_lib.lib().llark_pool_mean(_dev(h, "h", torch.float32), n, t, width, _opt(lens, "lens", torch.int32), _dev(out, "out"),
+                                     _stream()), "pool_mean")
     return out
 
 
@@ -480,12 +487,10 @@ def gemm16(a_hi: torch.Tensor, a_lo: Optional[torch.Tensor], wt: torch.Tensor, b
         # decode step: the weight-streaming LDS-DMA kernel (csrc/gemv_dma.hip)
         with _timed(name, 2.0 * m * n * kp):
             check(_lib.lib().llark_gemv16_dma(
-                int(a_lo is not None), epilogue, _dev(a_hi, "a_hi"), _dev(a_lo, "a_lo", dtype) if a_lo is not None else None, a_hi.stride(0),
-                _dev(wt, "wt"), wt.stride(0), _dev(bias, "bias", torch.float32) if bias is not None else None, m, n, kp,
-                _dev(c, "c", torch.float32) if c is not None else None, c.stride(0) if c is not None else 0,
-                _dev(resid, "resid", torch.float32) if resid is not None else None, resid.stride(0) if resid is not None else 0,
-                _dev(out_hi, "out_hi", dtype) if out_hi is not None else None, _dev(out_lo, "out_lo", dtype) if out_lo is not None else None,
-                out_hi.stride(0) if out_hi is not None else 0, _stream()), "gemv16_dma")
+                int(a_lo is not None), epilogue, _dev(a_hi, "a_hi"), _opt(a_lo, "a_lo", dtype), a_hi.stride(0),
+                _dev(wt, "wt"), wt.stride(0), _opt(bias, "bias", torch.float32), m, n, kp, _opt(c, "c", torch.float32), _ld(c),
+                _opt(resid, "resid", torch.float32), _ld(resid), _opt(out_hi, "out_hi", dtype), _opt(out_lo, "out_lo", dtype),
+                _ld(out_hi), _stream()), "gemv16_dma")
         return
     if variant < 0 and m >= FRAG_MIN_ROWS:
         fr = getattr(wt, "_llark_frag", None)
@@ -493,13 +498,10 @@ def gemm16(a_hi: torch.Tensor, a_lo: Optional[torch.Tensor], wt: torch.Tensor, b
             return gemm16_fragw(a_hi, a_lo, fr[0], bias, n, kp, epilogue, c=c, resid=resid, out_hi=out_hi, out_lo=out_lo, m=m)
     with _timed(name, 2.0 * m * n * kp):
       check(_lib.lib().llark_gemm16_ws(
-        variant, _DT[dtype], int(a_lo is not None), epilogue, _dev(a_hi, "a_hi"), _dev(a_lo, "a_lo", dtype) if a_lo is not None else None,
-        a_hi.stride(0), _dev(wt, "wt"), wt.stride(0), _dev(bias, "bias", torch.float32) if bias is not None else None,
-        m, n, kp, _dev(c, "c", torch.float32) if c is not None else None, c.stride(0) if c is not None else 0,
-        _dev(resid, "resid", torch.float32) if resid is not None else None, resid.stride(0) if resid is not None else 0,
-        _dev(out_hi, "out_hi", dtype) if out_hi is not None else None,
-        _dev(out_lo, "out_lo", dtype) if out_lo is not None else None,
-        out_hi.stride(0) if out_hi is not None else 0, workspace(), _stream()), "gemm16")
+        variant, _DT[dtype], int(a_lo is not None), epilogue, _dev(a_hi, "a_hi"), _opt(a_lo, "a_lo", dtype),
+        a_hi.stride(0), _dev(wt, "wt"), wt.stride(0), _opt(bias, "bias", torch.float32), m, n, kp, _opt(c, "c", torch.float32), _ld(c),
+        _opt(resid, "resid", torch.float32), _ld(resid), _opt(out_hi, "out_hi", dtype), _opt(out_lo, "out_lo", dtype),
+        _ld(out_hi), workspace(), _stream()), "gemm16")
 
 
 def gemm16_ln_takes(m: int, n: int, kp: int) -> bool:
@@ -531,14 +533,10 @@ def gemm16_ln(a_hi: torch.Tensor, a_lo: torch.Tensor, wt: torch.Tensor, bias: Op
     with _timed(name, 2.0 * m * n * kp):
         check(_lib.lib().llark_gemm16_ln_p(
             _DT[dtype], epilogue, _dev(a_hi, "a_hi"), _dev(a_lo, "a_lo", dtype), a_hi.stride(0), _dev(wt, "wt"), wt.stride(0),
-            _dev(bias, "bias", torch.float32) if bias is not None else None, m, n, kp,
-            _dev(c, "c", torch.float32) if c is not None else None, c.stride(0) if c is not None else 0,
-            _dev(resid, "resid", torch.float32) if resid is not None else None, resid.stride(0) if resid is not None else 0,
-            _dev(out_hi, "out_hi", dtype) if out_hi is not None else None, _dev(out_lo, "out_lo", dtype) if out_lo is not None else None,
-            out_hi.stride(0) if out_hi is not None else 0,
-            _dev(ln_stat, "ln_stat", torch.float32) if ln_stat is not None else None, _dev(ln_vec, "ln_vec", torch.float32),
-            _dev(ln_part, "ln_part", torch.float32) if ln_part is not None else None,
-            _dev(ln_pred, "ln_pred", torch.float32) if ln_pred is not None else None, workspace(), _stream()), "gemm16_ln")
+            _opt(bias, "bias", torch.float32), m, n, kp, _opt(c, "c", torch.float32), _ld(c), _opt(resid, "resid", torch.float32), _ld(resid),
+            _opt(out_hi, "out_hi", dtype), _opt(out_lo, "out_lo", dtype), _ld(out_hi), _opt(ln_stat, "ln_stat", torch.float32),
+            _dev(ln_vec, "ln_vec", torch.float32), _opt(ln_part, "ln_part", torch.float32), _opt(ln_pred, "ln_pred", torch.float32),
+            workspace(), _stream()), "gemm16_ln")
 
 
 def gemm16_lnp_fragw(a_hi: torch.Tensor, a_lo: torch.Tensor, wfrag: torch.Tensor, bias: Optional[torch.Tensor], n: int, kp: int,
@@ -559,10 +557,10 @@ def gemm16_lnp_fragw(a_hi: torch.Tensor, a_lo: torch.Tensor, wfrag: torch.Tensor
     with _timed(name, 2.0 * m * n * kp):
         check(_lib.lib().llark_gemm16_lnp_fragw(
             _DT[dtype], _dev(a_hi, "a_hi"), _dev(a_lo, "a_lo", dtype), a_hi.stride(0), _dev(wfrag, "wfrag"),
-            _dev(bias, "bias", torch.float32) if bias is not None else None, m, n, kp, _dev(c, "c", torch.float32), c.stride(0),
+            _opt(bias, "bias", torch.float32), m, n, kp, _dev(c, "c", torch.float32), c.stride(0),
             _dev(resid, "resid", torch.float32), resid.stride(0), _dev(out_hi, "out_hi", dtype), _dev(out_lo, "out_lo", dtype),
             out_hi.stride(0), _dev(ln_vec, "ln_vec", torch.float32), _dev(ln_part, "ln_part", torch.float32),
-            _dev(ln_pred, "ln_pred", torch.float32) if ln_pred is not None else None, _stream()), "gemm16_lnp_fragw")
+            _opt(ln_pred, "ln_pred", torch.float32), _stream()), "gemm16_lnp_fragw")
     return nparts
 
 
@@ -602,7 +600,7 @@ def gemm16_t(a: torch.Tensor, wt: torch.Tensor, m: int, n: int, kp: int, trans_a
             _dev(c, "c", torch.float32, contiguous=False) if accumulate else None, c.stride(0))
     with _timed("gemm_f16" if dtype == torch.float16 else "gemm_bf16", 2.0 * m * n * kp):
         if variant >= 0:                                   # explicit tile / pipeline variant (llark_gemm16_t_ex): benchmarks, A/B tests
-            check(_lib.lib().llark_gemm16_t_ex(int(variant), *args, _dev(sumsq, "sumsq", torch.float64) if sumsq is not None else None,
+            check(_lib.lib().llark_gemm16_t_ex(int(variant), *args, _opt(sumsq, "sumsq", torch.float64),
                                                _stream()), "gemm16_t_ex")
         elif sumsq is None:
             check(_lib.lib().llark_gemm16_t(*args, _stream()), "gemm16_t")
@@ -654,14 +652,9 @@ def gemm16_lo8(a_hi: torch.Tensor, a_lo8: torch.Tensor, wt: torch.Tensor, sw: in
     with _timed("gemm_lo8_f16", 2.0 * m * n * kp):
         check(_lib.lib().llark_gemm16_lo8(
             epilogue, _dev(a_hi, "a_hi"), _dev(a_lo8, "a_lo8"), a_hi.stride(0), a_lo8.stride(0), _dev(wt, "wt"), wt.stride(0),
-            _dev(w8, "w8", torch.uint8), w8.stride(0),
-            _dev(bias, "bias", torch.float32) if bias is not None else None, m, n, kp, int(sa), int(sw),
-            _dev(c, "c", torch.float32) if c is not None else None, c.stride(0) if c is not None else 0,
-            _dev(resid, "resid", torch.float32) if resid is not None else None, resid.stride(0) if resid is not None else 0,
-            _dev(out_hi, "out_hi", torch.float16) if out_hi is not None else None,
-            _dev(out_lo8, "out_lo8", torch.uint8) if out_lo8 is not None else None,
-            out_hi.stride(0) if out_hi is not None else 0, out_lo8.stride(0) if out_lo8 is not None else 0, workspace(), _stream()),
-            "gemm16_lo8")
+            _dev(w8, "w8", torch.uint8), w8.stride(0), _opt(bias, "bias", torch.float32), m, n, kp, int(sa), int(sw),
+            _opt(c, "c", torch.float32), _ld(c), _opt(resid, "resid", torch.float32), _ld(resid), _opt(out_hi, "out_hi", torch.float16),
+            _opt(out_lo8, "out_lo8", torch.uint8), _ld(out_hi), _ld(out_lo8), workspace(), _stream()), "gemm16_lo8")
 
 
 def lo8_max_rows(lda: int, lda8: int) -> int:
@@ -699,15 +692,15 @@ def gemm16_rmsnorm_a(x: torch.Tensor, norm_w: torch.Tensor, eps: float, wt: torc
         with _timed(name, 2.0 * m * n * kp):
             check(_lib.lib().llark_gemv16_dma_rmsnorm(
                 int(split), epilogue, _dev(x, "x", torch.float32), x.stride(0), _dev(norm_w, "norm_w", torch.float32), float(eps),
-                _dev(wt, "wt", bf), wt.stride(0), None, m, n, kp, _opt(c, "c", torch.float32), c.stride(0) if c is not None else 0,
-                _opt(out_hi, "out_hi", bf), _opt(out_lo, "out_lo", bf), out_hi.stride(0) if out_hi is not None else 0, _stream()),
+                _dev(wt, "wt", bf), wt.stride(0), None, m, n, kp, _opt(c, "c", torch.float32), _ld(c),
+                _opt(out_hi, "out_hi", bf), _opt(out_lo, "out_lo", bf), _ld(out_hi), _stream()),
                 "gemv16_dma_rmsnorm")
         return
     with _timed(name, 2.0 * m * n * kp):
         check(_lib.lib().llark_gemm16_rmsnorm_a(
             _DT[bf], int(split), epilogue, _dev(x, "x", torch.float32), x.stride(0), _dev(norm_w, "norm_w", torch.float32), float(eps),
-            _dev(wt, "wt", bf), wt.stride(0), None, m, n, kp, _opt(c, "c", torch.float32), c.stride(0) if c is not None else 0,
-            _opt(out_hi, "out_hi", bf), _opt(out_lo, "out_lo", bf), out_hi.stride(0) if out_hi is not None else 0, _stream()),
+            _dev(wt, "wt", bf), wt.stride(0), None, m, n, kp, _opt(c, "c", torch.float32), _ld(c),
+            _opt(out_hi, "out_hi", bf), _opt(out_lo, "out_lo", bf), _ld(out_hi), _stream()),
             "gemm16_rmsnorm_a")
 
 
@@ -742,13 +735,9 @@ def gemm16_fragw(a_hi: torch.Tensor, a_lo: Optional[torch.Tensor], wfrag: torch.
         variant = 0
     with _timed(name, 2.0 * m * n * kp):
       check(_lib.lib().llark_gemm16_fragw_sk(
-        variant, _DT[dtype], int(a_lo is not None), epilogue, _dev(a_hi, "a_hi"), _dev(a_lo, "a_lo", dtype) if a_lo is not None else None,
-        a_hi.stride(0), _dev(wfrag, "wfrag"), _dev(bias, "bias", torch.float32) if bias is not None else None,
-        m, n, kp, _dev(c, "c", torch.float32) if c is not None else None, c.stride(0) if c is not None else 0,
-        _dev(resid, "resid", torch.float32) if resid is not None else None, resid.stride(0) if resid is not None else 0,
-        _dev(out_hi, "out_hi", dtype) if out_hi is not None else None,
-        _dev(out_lo, "out_lo", dtype) if out_lo is not None else None,
-        out_hi.stride(0) if out_hi is not None else 0,
+        variant, _DT[dtype], int(a_lo is not None), epilogue, _dev(a_hi, "a_hi"), _opt(a_lo, "a_lo", dtype),
+        a_hi.stride(0), _dev(wfrag, "wfrag"), _opt(bias, "bias", torch.float32), m, n, kp, _opt(c, "c", torch.float32), _ld(c),
+        _opt(resid, "resid", torch.float32), _ld(resid), _opt(out_hi, "out_hi", dtype), _opt(out_lo, "out_lo", dtype), _ld(out_hi),
         scratch.data_ptr() if scratch is not None else None, scratch.numel() * 4 if scratch is not None else 0, _stream()), "gemm16_fragw")
 
 
@@ -803,12 +792,8 @@ def rmsnorm_bf16(x: torch.Tensor, w: torch.Tensor, eps: float, out_hi: torch.Ten
     rows, width = x.shape
     check(_lib.lib().llark_rmsnorm_bf16(_dev(x, "x", torch.float32), x.stride(0), rows, width, _dev(w, "w", torch.float32),
                                         float(eps), _dev(out_hi, "out_hi", torch.bfloat16),
-                                        _dev(out_lo, "out_lo", torch.bfloat16) if out_lo is not None else None,
+                                        _opt(out_lo, "out_lo", torch.bfloat16),
                                         out_hi.stride(0), _stream()), "rmsnorm_bf16")
-
-
-def _opt(t, name, dtype):
-    return _dev(t, name, dtype) if t is not None else None
 
 
 def rope_split_heads(qkv: torch.Tensor, batch: int, s: int, nh: int, hd: int, pos0: int, cos_t: torch.Tensor,
@@ -953,11 +938,11 @@ def decode_advance_rows(logits: Optional[torch.Tensor], state: torch.Tensor, nex
     if out_col is not None:
         assert out_col.dim() == 1 and out_col.shape[0] == batch and out_col.dtype == i64 and out_col.is_cuda
         ld_out = out_col.stride(0)
-    check(_lib.lib().llark_decode_advance_rows(_dev(logits, "logits", torch.float32, contiguous=False) if logits is not None else None, ldl,
+    check(_lib.lib().llark_decode_advance_rows(_opt(logits, "logits", torch.float32, contiguous=False), ldl,
                                                int(vocab), batch, _opt(choice, "choice", i64),
                                                _opt(pos_rows, "pos_rows", torch.int32), _dev(state, "state", torch.int32),
                                                _dev(next_ids, "next_ids", i64),
-                                               _dev(out_col, "out_col", i64, contiguous=False) if out_col is not None else None, ld_out,
+                                               _opt(out_col, "out_col", i64, contiguous=False), ld_out,
                                                int(eos), int(pad), _stream()), "decode_advance_rows")
 
 
@@ -1313,7 +1298,7 @@ def adamw_twins(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tens
     check(_lib.lib().llark_adamw_twins(
         _dev(p, "p"), _dev(g, "g", torch.float32), _dev(m, "m", torch.float32), _dev(v, "v", torch.float32), n, k, float(lr), float(beta1),
         float(beta2), float(eps), float(weight_decay), int(step), float(grad_scale),
-        _dev(grad_sumsq, "grad_sumsq", torch.float64) if grad_sumsq is not None else None, float(max_grad_norm),
+        _opt(grad_sumsq, "grad_sumsq", torch.float64), float(max_grad_norm),
         _opt(wfrag, "wfrag", bf), int(rope_rows), _opt(wtfrag, "wtfrag", bf), _stream()), "adamw_twins")
 
 
@@ -1375,7 +1360,7 @@ def gemm16_ta_fragw(a: torch.Tensor, wfrag: torch.Tensor, m: int, n: int, kp: in
         check(fn(
             EPI_RESID if accumulate else EPI_F32, _dev(a, "a", contiguous=False), a.stride(0), _dev(wfrag, "wfrag"), m, n, kp,
             _dev(c, "c", torch.float32, contiguous=False), c.stride(0), _dev(c, "c", torch.float32, contiguous=False) if accumulate else None,
-            c.stride(0), _dev(sumsq, "sumsq", torch.float64) if sumsq is not None else None, _stream()), "gemm16_ta_fragw")
+            c.stride(0), _opt(sumsq, "sumsq", torch.float64), _stream()), "gemm16_ta_fragw")
 
 
 def gemm16_fragw_rope_qkv_train(a: torch.Tensor, wfrag: torch.Tensor, kp: int, batch: int, s: int, nh: int, pos0: int, cos_t: torch.Tensor,
@@ -1425,11 +1410,11 @@ def gemv16_dma_chain(wt: torch.Tensor, n: int, epilogue: int, split: bool, a_hi=
     name = ("gemm_split_" if split else "gemm_") + "bf16_skinny"
     with _timed(name, 2.0 * n * kp):
         check(_lib.lib().llark_gemv16_dma_chain(
-            int(split), int(epilogue), _opt(a_hi, "a_hi", bf), _opt(a_lo, "a_lo", bf), a_hi.stride(0) if a_hi is not None else 0,
-            _opt(x, "x", f32), x.stride(0) if x is not None else 0, _opt(norm_w, "norm_w", f32), float(eps), _dev(wt, "wt", bf), wt.stride(0),
-            None, 1, n, kp, _opt(c, "c", f32), c.stride(0) if c is not None else 0, _opt(resid, "resid", f32),
-            resid.stride(0) if resid is not None else 0, _opt(out_hi, "out_hi", bf), _opt(out_lo, "out_lo", bf),
-            out_hi.stride(0) if out_hi is not None else 0, wait.data_ptr() if wait is not None else None, int(wait_target) & 0xFFFFFFFF,
+            int(split), int(epilogue), _opt(a_hi, "a_hi", bf), _opt(a_lo, "a_lo", bf), _ld(a_hi),
+            _opt(x, "x", f32), _ld(x), _opt(norm_w, "norm_w", f32), float(eps), _dev(wt, "wt", bf), wt.stride(0),
+            None, 1, n, kp, _opt(c, "c", f32), _ld(c), _opt(resid, "resid", f32),
+            _ld(resid), _opt(out_hi, "out_hi", bf), _opt(out_lo, "out_lo", bf),
+            _ld(out_hi), wait.data_ptr() if wait is not None else None, int(wait_target) & 0xFFFFFFFF,
             signal.data_ptr() if signal is not None else None, _stream()), "gemv16_dma_chain")
 
 

@@ -17,14 +17,14 @@ def _tables(smax):
     return freqs.cos().contiguous().cuda(), freqs.sin().contiguous().cuda()
 
 
-def _state(batch, split, seed):
+def _state(batch, split, seed, nh=NH, smax=SMAX):
     g = torch.Generator(device="cuda").manual_seed(seed)
     bf = torch.bfloat16
-    k = torch.randn((batch, NH, SMAX, HD), generator=g, device="cuda").to(bf)
-    vt = torch.randn((batch, NH, HD, SMAX), generator=g, device="cuda").to(bf)
+    k = torch.randn((batch, nh, smax, HD), generator=g, device="cuda").to(bf)
+    vt = torch.randn((batch, nh, HD, smax), generator=g, device="cuda").to(bf)
     kl = (torch.randn(k.shape, generator=g, device="cuda") * 2 ** -9).to(bf) if split else None
     vl = (torch.randn(vt.shape, generator=g, device="cuda") * 2 ** -9).to(bf) if split else None
-    qkv = torch.randn((batch, 3 * NH * HD), generator=g, device="cuda")
+    qkv = torch.randn((batch, 3 * nh * HD), generator=g, device="cuda")
     return qkv, [k, vt, kl, vl]
 
 
@@ -77,7 +77,7 @@ def _check_rows_equal_scalar(batch, split, pos_rows, alibi=None, seed=0):
 @pytest.mark.parametrize("batch", [1, 3, 8, 16])
 def test_rows_kernel_equals_scalar_position_kernel(batch, split):
     """Each row of the ragged launch is bit-identical to that row of the scalar launch at p = pos_rows[b] (same batch size: nh * batch
-    = 32, 96 < 256 and 256, 512 cross the wave-count switch of launch_attn_decode)."""
+    = 32, 96 < 256 and 256, 512 cross the wave-count switch of attn_decode() in csrc/llama.hip)."""
     if batch == 1:
         for i, p in enumerate(POSITIONS):
             _check_rows_equal_scalar(1, split, [p], seed=i)
@@ -110,6 +110,59 @@ def test_idle_rows_untouched_and_zero(split):
                     assert torch.equal(_bits(x[b]), _bits(y[b])), f"idle row {b}: cache slot changed"
     # the active rows next to them are still the scalar kernel's rows
     _check_rows_equal_scalar(batch, split, pos_rows, seed=3)
+
+
+@pytest.mark.parametrize("split", [True, False], ids=["split", "bf16"])
+def test_decode_forms_agree_beyond_the_default_lds_limit(split):
+    """smax = 12296 keys: 4 * 12296 bytes of scores is the first multiple-of-8 cache length whose dynamic LDS exceeds the 48 KiB a kernel
+    gets by default, so every entry point has to raise its limit on first use -- the host position (LDS sized from the 12291 visible
+    keys, rounded up to 8) as well as the device positions (sized from smax).  Position 12290, one sequence, two heads.  The five decode
+    forms, each used here for the first time in this order, leave bit-identical output heads and bit-identical caches."""
+    from llark_amd import ops
+    nh, smax, p, bf = 2, 12296, 12290, torch.bfloat16
+    assert 4 * smax > 48 * 1024 >= 4 * (smax - 8) and 4 * ((p + 1 + 7) // 8 * 8) > 48 * 1024
+    cos, sin = _tables(smax)
+    qkv, caches = _state(1, split, 21, nh=nh, smax=smax)
+    pos_dev = torch.tensor([p], dtype=torch.int32, device="cuda")
+
+    def outputs():
+        out = torch.full((1, nh * HD), 7.0, dtype=bf, device="cuda")
+        return out, (torch.full_like(out, 7.0) if split else None)
+
+    def fused(fn, pos):
+        c, (out, out_lo) = _clone(caches), outputs()
+        fn(qkv, 1, nh, HD, pos, cos, sin, c[0], c[1], out, c[2], c[3], out_lo)
+        return out, out_lo, c
+
+    def unfused(dpos):
+        c, (out, out_lo) = _clone(caches), outputs()
+        q = torch.empty((1, nh, 1, HD), dtype=bf, device="cuda")
+        q_lo = torch.empty_like(q) if split else None
+        if dpos:
+            ops.rope_split_heads_dpos(qkv, 1, nh, HD, pos_dev, cos, sin, q, c[0], c[1], q_lo, c[2], c[3])
+            ops.attn_decode_dpos(q, c[0], c[1], 1, nh, HD, pos_dev, out, q_lo, c[2], c[3], out_lo)
+        else:
+            ops.rope_split_heads(qkv, 1, 1, nh, HD, p, cos, sin, q, c[0], c[1], q_lo, c[2], c[3])
+            ops.attn_decode(q, c[0], c[1], 1, nh, HD, p + 1, out, q_lo, c[2], c[3], out_lo)
+        return out, out_lo, c
+
+    runs = [("attn_decode_rope, host position", fused(ops.attn_decode_rope, p)),
+            ("attn_decode_rope, device position", fused(ops.attn_decode_rope, pos_dev)),
+            ("attn_decode_rope_rows", fused(ops.attn_decode_rope_rows, pos_dev)),
+            ("rope_split_heads + attn_decode", unfused(False)),
+            ("rope_split_heads_dpos + attn_decode_dpos", unfused(True))]
+    torch.cuda.synchronize()
+    ref_name, (ref_out, ref_lo, ref_c) = runs[0]
+    assert ref_out.float().isfinite().all() and (ref_out.float() != 7.0).any()
+    assert not torch.equal(_bits(ref_c[0][0, :, p]), _bits(caches[0][0, :, p])), "the new key row was not written"
+    assert not torch.equal(_bits(ref_c[1][0, :, :, p]), _bits(caches[1][0, :, :, p])), "the new value column was not written"
+    for name, (out, out_lo, c) in runs[1:]:
+        assert torch.equal(_bits(out), _bits(ref_out)), f"{name}: output differs from {ref_name}"
+        if split:
+            assert torch.equal(_bits(out_lo), _bits(ref_lo)), f"{name}: output lo plane differs from {ref_name}"
+        for cname, x, y in zip(("k", "vt", "k_lo", "vt_lo"), c, ref_c):
+            if x is not None:
+                assert torch.equal(_bits(x), _bits(y)), f"{name}: {cname} cache differs from {ref_name}"
 
 
 def test_decode_advance_rows_matches_argmax_and_bookkeeping():
