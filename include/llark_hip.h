@@ -158,6 +158,11 @@ int llark_vqvae_fix_near_ties(void* plan, const float* audio, int n, int t_sampl
  * ------------------------------------------------------------------------------------------- */
 int llark_prior_embed(const int64_t* z, int n, int t, int width, int bins, const float* x_emb, const float* pos_emb,
                       const float* x_cond, const float* y_cond, float* h, llark_stream_t stream);
+/* The head of a forward in one pass: llark_prior_embed + llark_layernorm_split_f16 (gamma, beta: block 0's ln_0) + -- pred != NULL --
+ * llark_ln_row_pred, every output (h, the planes, pred [n*t][2]) bit-equal to that sequence.  width % 8 == 0, width <= 8192, ldo % 8 == 0. */
+int llark_prior_head(const int64_t* z, int n, int t, int width, int bins, const float* x_emb, const float* pos_emb,
+                     const float* x_cond, const float* y_cond, const float* gamma, const float* beta, float eps, float* h,
+                     void* out_hi, void* out_lo, int ldo, float* pred, llark_stream_t stream);
 /* LayerNorm(width, eps) in fp32 -> fp16 hi/lo planes [rows][ldo] */
 int llark_layernorm_split_f16(const float* x, int ldx, int rows, int width, const float* gamma, const float* beta,
                               float eps, void* out_hi, void* out_lo, int ldo, llark_stream_t stream);
@@ -173,6 +178,13 @@ int llark_prior_attn_lo8(const float* qkv, int ldq, int n, int t, int n_state, i
 /* AvgPool1d(frame_len, stride=frame_len, ceil_mode=False) over time: h [n][t][width] -> out [n][frames][width] */
 int llark_pool_window(const float* h, int n, int t, int width, int frame_len, float* out, int frames,
                       llark_stream_t stream);
+/* llark_pool_window moved in front of the last block's second MLP product (pooling is linear over rows): one pass over the fp32
+ * stream h [n][t][width] and the fp16 planes g_hi / g_lo [n*t][ldg] (gwidth valid columns) writes pool_h [n*frames][width] -- bit-equal
+ * to llark_pool_window -- and pg_hi / pg_lo [n*frames][ldg]: the window mean of float(hi) + float(lo), summed in fp32 in row order and
+ * split again like the GEMM epilogues; columns [gwidth, ldg) are written as zeros.  Windows never cross a clip; rows past
+ * frames * frame_len are not read.  width % 4 == 0, ldg % 8 == 0, pointers 16-byte aligned. */
+int llark_pool_window_tail(const float* h, const void* g_hi, const void* g_lo, int n, int t, int width, int gwidth, int ldg,
+                           int frame_len, int frames, float* pool_h, void* pg_hi, void* pg_lo, llark_stream_t stream);
 /* acts[:len].mean(0): lens is a device int[n] (NULL -> t) */
 int llark_pool_mean(const float* h, int n, int t, int width, const int* lens, float* out, llark_stream_t stream);
 int llark_zero_pad16(void* plane, int rows, int ld, int from, llark_stream_t stream);
@@ -314,6 +326,13 @@ int llark_gemm16_batched(int dtype, int split, int epilogue, const void* a_hi, c
                          const void* wt, int ldw, long long stride_w, int m, int n, int kp, float* c, int ldc,
                          long long stride_c, void* out_hi, void* out_lo, int ldo, long long stride_o, int batch,
                          llark_stream_t stream);
+/* The same with a bias [n] shared by every batch element and a per-element residual (epilogue F32: c = A . wt^T + bias; RESID: + resid).
+ * Every element is bit-equal to its own llark_gemm16_ws call with the same m: elements of m <= 16 rows are launched one by one on the
+ * weight-streaming kernel, larger ones share one launch of the tile kernel; shapes of the persistent tiles are refused. */
+int llark_gemm16_batched_bias(int dtype, int split, int epilogue, const void* a_hi, const void* a_lo, int lda, long long stride_a,
+                              const void* wt, int ldw, long long stride_w, const float* bias, int m, int n, int kp, float* c, int ldc,
+                              long long stride_c, const float* resid, int ldr, long long stride_r, void* out_hi, void* out_lo, int ldo,
+                              long long stride_o, int batch, llark_stream_t stream);
 /* w[k][n] (upstream Conv1D.w, 16-bit) -> wt[n][ldw] with zero K padding; also serves row-major copies
  * (transpose=0: w is already [n][k], e.g. nn.Linear.weight). src_dtype/dst_dtype: LLARK_F16/BF16 or
  * 2 for fp32 source. */

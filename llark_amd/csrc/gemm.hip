@@ -1316,6 +1316,31 @@ extern "C" int llark_gemm16_batched(int dtype, int split, int epilogue, const vo
                        ldo, batch, stride_a, stride_w, stride_c, 0, stride_o, stream);
 }
 
+// llark_gemm16_batched with a bias [n] shared by every batch element and a per-element residual: one product per CLIP, so that a clip's
+// rows come out of the same kernel at the same m whatever batch it rides in (the mm_projector, each clip's rows landing in its own
+// sequence of the hidden state: stride_c = S * hidden; the prior's pooled last product, m = frames).
+extern "C" int llark_gemm16_batched_bias(int dtype, int split, int epilogue, const void* a_hi, const void* a_lo, int lda,
+                                         long long stride_a, const void* wt, int ldw, long long stride_w, const float* bias, int m, int n,
+                                         int kp, float* c, int ldc, long long stride_c, const float* resid, int ldr, long long stride_r,
+                                         void* out_hi, void* out_lo, int ldo, long long stride_o, int batch, llark_stream_t stream) {
+    LLARK_REQUIRE(batch >= 1 && batch <= 65535, "gemm16_batched_bias: batch %d out of range", batch);
+    // Every element must come out bit-equal to its own llark_gemm16_ws call.  The tile kernels take the batch as a grid dimension; the skinny
+    // weight-streaming kernels (m <= 16, another K order) do not, so those elements are launched one by one; the persistent tiles are refused.
+    LLARK_REQUIRE(m <= 16 || pick_variant(split, m, n, kp, true) < 20, "gemm16_batched_bias: m=%d n=%d kp=%d is a persistent-tile shape (use llark_gemm16_ws per element)", m, n, kp);
+    if (m <= 16 && batch > 1) {
+        for (int b = 0; b < batch; ++b) {
+            const int rc = gemm16_impl(-1, dtype, split, epilogue, (const char*)a_hi + 2 * b * stride_a, a_lo ? (const char*)a_lo + 2 * b * stride_a : nullptr, lda,
+                                       (const char*)wt + 2 * b * stride_w, ldw, bias, m, n, kp, c ? c + b * stride_c : nullptr, ldc, resid ? resid + b * stride_r : nullptr, ldr,
+                                       out_hi ? (char*)out_hi + 2 * b * stride_o : nullptr, out_lo ? (char*)out_lo + 2 * b * stride_o : nullptr, ldo,
+                                       0, 0, 0, 0, 0, 0, stream);
+            if (rc != LLARK_OK) return rc;
+        }
+        return LLARK_OK;
+    }
+    return gemm16_impl(-1, dtype, split, epilogue, a_hi, a_lo, lda, wt, ldw, bias, m, n, kp, c, ldc, resid, ldr, out_hi, out_lo,
+                       ldo, batch, stride_a, stride_w, stride_c, stride_r, stride_o, stream);
+}
+
 extern "C" int llark_gemm16(int dtype, int split, int epilogue, const void* a_hi, const void* a_lo, int lda,
                             const void* wt, int ldw, const float* bias, int m, int n, int kp, float* c, int ldc,
                             const float* resid, int ldr, void* out_hi, void* out_lo, int ldo, llark_stream_t stream) {

@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "gemm_core.h"      // fp_pin / sub_hi: the hi / lo split of the GEMM epilogues
 
 namespace llark {
 
@@ -192,16 +193,47 @@ __global__ __launch_bounds__(256) void layernorm_split8_kernel(const float* __re
 // Row statistics of a LayerNorm whose partial sums came out of a GEMM epilogue (llark_gemm16_ln, producer role): part [rows][nparts][2] =
 // (sum, sum of squares) over 128-column slices, summed here in slice order (fixed: run-to-run bit-equal) in double -> stat [rows][2] =
 // (mean, 1 / sqrt(var + eps)), var = E[x^2] - mean^2 (biased, like torch layer_norm).
+// A row's partials, summed in slice order.  VEC (nparts even, part 16-byte aligned: every row then starts on 16 bytes): the loads go out ten
+// 16-byte loads (twenty slices) at a time BEFORE the sums that wait for them -- one thread owns a row, so a load per dependent add left the
+// kernel waiting out a memory latency per slice (17 us per launch at 65536 x 38) -- and the additions keep their order: bit-equal.
+template <bool VEC>
+__device__ __forceinline__ void ln_row_partial_sums(const float* __restrict__ part, int r, int nparts, double& sx, double& sq) {
+    sx = 0.0;
+    sq = 0.0;
+    if (VEC) {
+        const float4* pr = (const float4*)(part + (size_t)r * nparts * 2);
+        const int n4 = nparts >> 1;
+        for (int i0 = 0; i0 < n4; i0 += 10) {
+            float4 v[10];
+#pragma unroll
+            for (int j = 0; j < 10; ++j)
+                if (i0 + j < n4) v[j] = pr[i0 + j];
+#pragma unroll
+            for (int j = 0; j < 10; ++j) {
+                if (i0 + j < n4) {
+                    sx += (double)v[j].x;
+                    sq += (double)v[j].y;
+                    sx += (double)v[j].z;
+                    sq += (double)v[j].w;
+                }
+            }
+        }
+    } else {
+        const float2* pr = (const float2*)(part + (size_t)r * nparts * 2);
+        for (int i = 0; i < nparts; ++i) {
+            const float2 v = pr[i];
+            sx += (double)v.x;
+            sq += (double)v.y;
+        }
+    }
+}
+
+template <bool VEC>
 __global__ void ln_stats_finalize_kernel(const float* __restrict__ part, int rows, int nparts, int width, float eps, float* __restrict__ stat) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= rows) return;
-    const float2* pr = (const float2*)(part + (size_t)r * nparts * 2);
-    double sx = 0.0, sq = 0.0;
-    for (int i = 0; i < nparts; ++i) {
-        const float2 v = pr[i];
-        sx += (double)v.x;
-        sq += (double)v.y;
-    }
+    double sx, sq;
+    ln_row_partial_sums<VEC>(part, r, nparts, sx, sq);
     const double mean = sx / (double)width;
     double var = sq / (double)width - mean * mean;
     var = var > 0.0 ? var : 0.0;
@@ -221,17 +253,13 @@ __device__ __forceinline__ float pow2_near(float v) {          // nearest power 
     e = e < -24 ? -24 : (e > 24 ? 24 : e);
     return ldexpf(1.0f, e);
 }
+template <bool VEC>
 __global__ void ln_stats_finalize_p_kernel(const float* __restrict__ part, int rows, int nparts, int width, float eps, float* __restrict__ stat,
                                            float* __restrict__ pred) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= rows) return;
-    const float2* pr = (const float2*)(part + (size_t)r * nparts * 2);
-    double sx = 0.0, sq = 0.0;
-    for (int i = 0; i < nparts; ++i) {
-        const float2 v = pr[i];
-        sx += (double)v.x;
-        sq += (double)v.y;
-    }
+    double sx, sq;
+    ln_row_partial_sums<VEC>(part, r, nparts, sx, sq);
     const float2 pd = *(const float2*)(pred + 2 * (size_t)r);
     const double dm = sx / (double)width;
     double var = sq / (double)width - dm * dm;
@@ -259,6 +287,124 @@ __global__ __launch_bounds__(256) void ln_row_pred_kernel(const float* __restric
     double var = sq / (double)width - mean * mean;
     var = var > 0.0 ? var : 0.0;
     if (lane == 0) *(float2*)(pred + 2 * (size_t)row) = make_float2((float)mean, pow2_near((float)(1.0 / sqrt(var + (double)eps))));
+}
+
+// The head of a folded chain in one pass: prior_embed_kernel + layernorm_split8_kernel<NG, false> of block 0 + (pred != nullptr)
+// ln_row_pred_kernel, one wave per row with the embedded row in registers -- the stream is written once and never read back.  Every output is
+// bit-equal to the three kernels: the same association ((x_emb | y_cond) + pos_emb) + x_cond, the same two-pass variance over the same
+// lane-to-column map (8 consecutive columns per lane), and for pred the same per-lane partial sums -- ln_row_pred_kernel gives lane l the
+// float4 groups l, l + 64, ...: each group's (sum, sum of squares) goes through this wave's LDS slice [width / 4] to the lane that owns it there.
+template <int NG>
+__global__ __launch_bounds__(256) void prior_head_kernel(const long long* __restrict__ z, const float4* __restrict__ x_emb,
+                                                         const float4* __restrict__ pos_emb, const float4* __restrict__ x_cond,
+                                                         const float4* __restrict__ y_cond, int rows, int t, int width, int bins,
+                                                         const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                         float* __restrict__ hout, half_t* __restrict__ hi, half_t* __restrict__ lo, int ldo,
+                                                         float* __restrict__ pred) {
+    extern __shared__ float2 head_fg[];                       // [4 waves][width / 4] (sum, sum of squares) of each float4 group
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int w8 = width >> 3, w4 = width >> 2;
+    const int tt = row % t;
+    const float4* er;
+    if (tt == 0) {
+        er = y_cond;
+    } else {
+        long long code = z[row - 1];                          // z [n][t]: the previous token of the same clip
+        code = code < 0 ? 0 : (code >= bins ? bins - 1 : code);
+        er = x_emb + (size_t)code * w4;
+    }
+    const float4* pr = pos_emb + (size_t)tt * w4;
+    const float4* cr = x_cond + (size_t)tt * w4;
+    float4* xr = (float4*)(hout + (size_t)row * width);
+    float2* fg = head_fg + (size_t)(threadIdx.x >> 6) * w4;
+    float4 v[NG][2];
+    float s = 0.0f;
+#pragma unroll
+    for (int k = 0; k < NG; ++k) {
+        const int c = lane + 64 * k;
+        if (c < w8) {
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+                const float4 e = er[2 * c + hf], pe = pr[2 * c + hf], xc = cr[2 * c + hf];
+                float4 o;
+                o.x = (e.x + pe.x) + xc.x;
+                o.y = (e.y + pe.y) + xc.y;
+                o.z = (e.z + pe.z) + xc.z;
+                o.w = (e.w + pe.w) + xc.w;
+                v[k][hf] = o;
+                xr[2 * c + hf] = o;
+            }
+            s += ((v[k][0].x + v[k][0].y) + (v[k][0].z + v[k][0].w)) + ((v[k][1].x + v[k][1].y) + (v[k][1].z + v[k][1].w));
+            if (pred != nullptr) {
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf) {
+                    const float4 a = v[k][hf];
+                    fg[2 * c + hf] = make_float2((a.x + a.y) + (a.z + a.w), (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w));
+                }
+            }
+        } else {
+            v[k][0] = v[k][1] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+    if (pred != nullptr) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");            // this wave's LDS writes, then its reads of other lanes' groups
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        float ps = 0.f, pq = 0.f;
+        for (int c = lane; c < w4; c += 64) {
+            const float2 a = fg[c];
+            ps += a.x;
+            pq += a.y;
+        }
+        const double sum = (double)wave_sum(ps), sq = (double)wave_sum(pq);
+        const double pmean = sum / (double)width;
+        double pvar = sq / (double)width - pmean * pmean;
+        pvar = pvar > 0.0 ? pvar : 0.0;
+        if (lane == 0) *(float2*)(pred + 2 * (size_t)row) = make_float2((float)pmean, pow2_near((float)(1.0 / sqrt(pvar + (double)eps))));
+    }
+    const float mean = wave_sum(s) / (float)width;
+    float q = 0.0f;
+#pragma unroll
+    for (int k = 0; k < NG; ++k) {
+        if (lane + 64 * k < w8) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const float a = v[k][h].x - mean, b = v[k][h].y - mean, cc = v[k][h].z - mean, d = v[k][h].w - mean;
+                q += (a * a + b * b) + (cc * cc + d * d);
+            }
+        }
+    }
+    const float var = wave_sum(q) / (float)width;
+    const float rstd = 1.0f / sqrtf(var + eps);
+    const float4* g4 = (const float4*)gamma;
+    const float4* b4 = (const float4*)beta;
+    half_t* hr = hi + (size_t)row * ldo;
+    half_t* lr = lo + (size_t)row * ldo;
+#pragma unroll
+    for (int k = 0; k < NG; ++k) {
+        const int c = lane + 64 * k;
+        if (c < w8) {
+            half8_t h, l16;
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+                const float4 g = g4[2 * c + hf], b = b4[2 * c + hf];
+                float y[4];
+                y[0] = (v[k][hf].x - mean) * rstd * g.x + b.x;
+                y[1] = (v[k][hf].y - mean) * rstd * g.y + b.y;
+                y[2] = (v[k][hf].z - mean) * rstd * g.z + b.z;
+                y[3] = (v[k][hf].w - mean) * rstd * g.w + b.w;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    h[4 * hf + e] = (half_t)y[e];
+                    l16[4 * hf + e] = (half_t)(y[e] - (float)h[4 * hf + e]);
+                }
+            }
+            *(half8_t*)(hr + 8 * c) = h;
+            *(half8_t*)(lr + 8 * c) = l16;
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -883,6 +1029,55 @@ __global__ void pool_window_kernel(const float* __restrict__ h, float* __restric
     }
 }
 
+// The same windowed mean applied BEFORE the last block's second MLP product (pooling is linear over rows and nothing follows that
+// product): one pass writes pool(h) -- per column the arithmetic of pool_window_kernel, so bit-equal to it -- and the hi / lo planes of
+// pool(g), g = float(hi) + float(lo) accumulated in fp32 over the window's rows in ascending order and split again as the GEMM
+// epilogues split (fp_pin / sub_hi).  Columns [gwidth, ldg) of the pooled planes are written as zeros whatever the input holds there.
+// One workgroup per (frame, clip); a thread owns 4 columns of h (16-byte loads) or 8 columns of both planes (16-byte loads each).
+__global__ __launch_bounds__(256) void pool_window_tail_kernel(const float* __restrict__ h, const half_t* __restrict__ g_hi,
+                                                               const half_t* __restrict__ g_lo, float* __restrict__ pool_h,
+                                                               half_t* __restrict__ pg_hi, half_t* __restrict__ pg_lo, int t, int width,
+                                                               int gwidth, int ldg, int frame_len, int frames) {
+    const int f = blockIdx.x, n = blockIdx.y;
+    const size_t row0 = (size_t)n * t + (size_t)f * frame_len;
+    const size_t orow = (size_t)n * frames + f;
+    const int w4 = width >> 2, g8 = ldg >> 3;
+    const float fl = (float)frame_len;
+    for (int item = threadIdx.x; item < w4 + g8; item += blockDim.x) {
+        if (item < w4) {
+            const float4* src = (const float4*)(h + row0 * width) + item;
+            float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 4
+            for (int i = 0; i < frame_len; ++i) {
+                const float4 v = src[(size_t)i * w4];
+                s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+            }
+            ((float4*)(pool_h + orow * width))[item] = make_float4(s.x / fl, s.y / fl, s.z / fl, s.w / fl);
+        } else {
+            const int c = item - w4;
+            const half8_t* sh = (const half8_t*)(g_hi + row0 * ldg) + c;
+            const half8_t* sl = (const half8_t*)(g_lo + row0 * ldg) + c;
+            float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+            for (int i = 0; i < frame_len; ++i) {
+                const half8_t a = sh[(size_t)i * g8], b = sl[(size_t)i * g8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) s[e] += (float)a[e] + (float)b[e];
+            }
+            half8_t oh, ol;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float x = 8 * c + e < gwidth ? fp_pin(s[e] / fl) : 0.0f;
+                const half_t hh = (half_t)x;
+                oh[e] = hh;
+                ol[e] = (half_t)sub_hi<half_t>(x, hh);
+            }
+            ((half8_t*)(pg_hi + orow * ldg))[c] = oh;
+            ((half8_t*)(pg_lo + orow * ldg))[c] = ol;
+        }
+    }
+}
+
 __global__ void pool_mean_kernel(const float* __restrict__ h, float* __restrict__ out, int t, int width,
                                  const int* __restrict__ lens) {
     const int n = blockIdx.y;
@@ -922,6 +1117,30 @@ extern "C" int llark_prior_embed(const int64_t* z, int n, int t, int width, int 
                                                                 (const float4*)pos_emb, (const float4*)x_cond,
                                                                 (const float4*)y_cond, (float4*)h, n, t, width / 4, bins);
     return check_launch("prior_embed");
+}
+
+extern "C" int llark_prior_head(const int64_t* z, int n, int t, int width, int bins, const float* x_emb, const float* pos_emb,
+                                const float* x_cond, const float* y_cond, const float* gamma, const float* beta, float eps, float* h,
+                                void* out_hi, void* out_lo, int ldo, float* pred, llark_stream_t stream) {
+    LLARK_REQUIRE(z && x_emb && pos_emb && x_cond && y_cond && gamma && beta && h && out_hi && out_lo, "prior_head: null pointer");
+    LLARK_REQUIRE(n > 0 && t > 0 && bins > 0 && width > 0 && width % 8 == 0 && width <= 8192 && ldo % 8 == 0 && ldo >= width &&
+                  (long long)n * t <= 0x7FFFFFFF, "prior_head: bad shape n=%d t=%d width=%d ldo=%d (width, ldo multiples of 8; width <= 8192)", n, t, width, ldo);
+    LLARK_REQUIRE(((uintptr_t)h & 15) == 0 && ((uintptr_t)out_hi & 15) == 0 && ((uintptr_t)out_lo & 15) == 0 && ((uintptr_t)x_emb & 15) == 0 &&
+                  ((uintptr_t)pos_emb & 15) == 0 && ((uintptr_t)x_cond & 15) == 0 && ((uintptr_t)y_cond & 15) == 0 && ((uintptr_t)gamma & 15) == 0 &&
+                  ((uintptr_t)beta & 15) == 0 && (!pred || ((uintptr_t)pred & 7) == 0), "prior_head: pointers must be 16-byte aligned");
+    const int rows = n * t, w8 = width / 8;
+    const size_t lds = (size_t)4 * (width / 4) * sizeof(float2);             // <= 64 KiB
+    hipStream_t s = (hipStream_t)stream;
+#define HEAD_CASE(NG)                                                                                                                        \
+    prior_head_kernel<NG><<<cdiv(rows, 4), 256, lds, s>>>((const long long*)z, (const float4*)x_emb, (const float4*)pos_emb, (const float4*)x_cond, \
+                                                         (const float4*)y_cond, rows, t, width, bins, gamma, beta, eps, h, (half_t*)out_hi,  \
+                                                         (half_t*)out_lo, ldo, pred)
+    if (w8 <= 64) HEAD_CASE(1);
+    else if (w8 <= 256) HEAD_CASE(4);
+    else if (w8 <= 640) HEAD_CASE(10);
+    else HEAD_CASE(16);
+#undef HEAD_CASE
+    return check_launch("prior_head");
 }
 
 static int layernorm_split_impl(const float* x, int ldx, int rows, int width, const float* gamma, const float* beta, float eps,
@@ -969,13 +1188,15 @@ static int layernorm_split_impl(const float* x, int ldx, int rows, int width, co
 
 extern "C" int llark_ln_stats_finalize(const float* part, int rows, int nparts, int width, float eps, float* stat, llark_stream_t stream) {
     LLARK_REQUIRE(part && stat && rows > 0 && nparts > 0 && width > 0, "ln_stats_finalize: bad arguments");
-    ln_stats_finalize_kernel<<<cdiv(rows, 256), 256, 0, (hipStream_t)stream>>>(part, rows, nparts, width, eps, stat);
+    if (nparts % 2 == 0 && ((uintptr_t)part & 15) == 0) ln_stats_finalize_kernel<true><<<cdiv(rows, 256), 256, 0, (hipStream_t)stream>>>(part, rows, nparts, width, eps, stat);
+    else ln_stats_finalize_kernel<false><<<cdiv(rows, 256), 256, 0, (hipStream_t)stream>>>(part, rows, nparts, width, eps, stat);
     return check_launch("ln_stats_finalize");
 }
 
 extern "C" int llark_ln_stats_finalize_p(const float* part, int rows, int nparts, int width, float eps, float* stat, float* pred, llark_stream_t stream) {
     LLARK_REQUIRE(part && stat && pred && rows > 0 && nparts > 0 && width > 0, "ln_stats_finalize_p: bad arguments");
-    ln_stats_finalize_p_kernel<<<cdiv(rows, 256), 256, 0, (hipStream_t)stream>>>(part, rows, nparts, width, eps, stat, pred);
+    if (nparts % 2 == 0 && ((uintptr_t)part & 15) == 0) ln_stats_finalize_p_kernel<true><<<cdiv(rows, 256), 256, 0, (hipStream_t)stream>>>(part, rows, nparts, width, eps, stat, pred);
+    else ln_stats_finalize_p_kernel<false><<<cdiv(rows, 256), 256, 0, (hipStream_t)stream>>>(part, rows, nparts, width, eps, stat, pred);
     return check_launch("ln_stats_finalize_p");
 }
 
@@ -1081,6 +1302,21 @@ extern "C" int llark_pool_window(const float* h, int n, int t, int width, int fr
     dim3 grid(frames, n);
     pool_window_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(h, out, t, width, frame_len, frames);
     return check_launch("pool_window");
+}
+
+extern "C" int llark_pool_window_tail(const float* h, const void* g_hi, const void* g_lo, int n, int t, int width, int gwidth, int ldg,
+                                      int frame_len, int frames, float* pool_h, void* pg_hi, void* pg_lo, llark_stream_t stream) {
+    LLARK_REQUIRE(h && g_hi && g_lo && pool_h && pg_hi && pg_lo, "pool_window_tail: null pointer");
+    LLARK_REQUIRE(n > 0 && t > 0 && frame_len > 0 && frames > 0 && width > 0 && gwidth > 0, "pool_window_tail: bad arguments");
+    LLARK_REQUIRE((long)frames * frame_len <= t, "pool_window_tail: %d frames of %d exceed %d rows", frames, frame_len, t);
+    LLARK_REQUIRE(width % 4 == 0 && ldg % 8 == 0 && ldg >= gwidth, "pool_window_tail: width=%d must be a multiple of 4, ldg=%d a multiple of 8 covering gwidth=%d",
+                  width, ldg, gwidth);
+    LLARK_REQUIRE(((uintptr_t)h & 15) == 0 && ((uintptr_t)pool_h & 15) == 0 && ((uintptr_t)g_hi & 15) == 0 && ((uintptr_t)g_lo & 15) == 0 &&
+                  ((uintptr_t)pg_hi & 15) == 0 && ((uintptr_t)pg_lo & 15) == 0, "pool_window_tail: pointers must be 16-byte aligned");
+    dim3 grid(frames, n);
+    pool_window_tail_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(h, (const half_t*)g_hi, (const half_t*)g_lo, pool_h, (half_t*)pg_hi, (half_t*)pg_lo,
+                                                                  t, width, gwidth, ldg, frame_len, frames);
+    return check_launch("pool_window_tail");
 }
 
 extern "C" int llark_pool_mean(const float* h, int n, int t, int width, const int* lens, float* out,

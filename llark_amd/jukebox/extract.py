@@ -120,14 +120,15 @@ def get_cond(hps, top_prior: TopPrior):
     return x_cond[0, : top_prior.n_ctx][None, ...], y_cond[0][None, ...]
 
 
-def get_final_activations(z, x_cond, y_cond, top_prior: TopPrior):
+def get_final_activations(z, x_cond, y_cond, top_prior: TopPrior, pool=None):
+    """``pool=(frame_len, frames)`` (NEW): the windowed mean of the activations, see ``PriorTransformer.forward``."""
     x = z[:, : top_prior.n_ctx]
 
     # make sure that we get the activations
     top_prior.prior.only_encode = True
 
     # encoder_kv and fp16 are set to the defaults, but explicitly so
-    out = top_prior.prior.forward(x, x_cond=x_cond, y_cond=y_cond, encoder_kv=None, fp16=False)
+    out = top_prior.prior.forward(x, x_cond=x_cond, y_cond=y_cond, encoder_kv=None, fp16=False, pool=pool)
 
     return out
 
@@ -158,6 +159,26 @@ def _postprocess(acts: torch.Tensor, latent_audio_len: int, meanpool: bool, pool
     return acts
 
 
+def _window_frames(lens, meanpool: bool, pool_frames_per_second, acts_sample_rate: float, n_ctx: int):
+    """(frame_len, frames over n_ctx) when every clip's pooling is the windowed mean with at least one window -- the forward can then
+    pool before the last block's second MLP product (``PriorTransformer.forward(pool=)``: windows start at row 0, so a clip of
+    ``len`` rows keeps the first ``len // frame_len`` of them) -- else None: the global mean and the unpooled output need every row."""
+    if not (meanpool and pool_frames_per_second):
+        return None
+    frame_len = floor(acts_sample_rate / pool_frames_per_second)
+    if frame_len < 1 or min(lens) < frame_len:
+        return None
+    return frame_len, n_ctx // frame_len
+
+
+def _postprocess_pooled(pooled: torch.Tensor, latent_audio_len: int, frame_len: int, pool_frames_per_second) -> np.ndarray:
+    """:func:`_postprocess` of one clip whose windows were already averaged: pooled (frames, width) on device."""
+    logging.warning(f"mean pooling at f={pool_frames_per_second}")
+    acts = pooled[: latent_audio_len // frame_len].cpu().numpy().copy()
+    logging.info(f"acts after pooling has shape {acts.shape}")
+    return acts
+
+
 def get_acts_from_audio(audio: np.ndarray, hps, vqvae, top_prior, meanpool=True, pool_frames_per_second=None):
     """``get_acts_from_file`` after the decode step (waveform already mono / normalised)."""
     expected = vqvae.sample_length
@@ -168,10 +189,14 @@ def get_acts_from_audio(audio: np.ndarray, hps, vqvae, top_prior, meanpool=True,
 
     z = get_z(audio, vqvae)                       # [1, T]
     x_cond, y_cond = get_cond(hps, top_prior)
-    acts = get_final_activations(z, x_cond, y_cond, top_prior)
-    acts = acts.squeeze(0).type(torch.float32)
     acts_rate = n_ctx / (expected / hps.sr)
-    return _postprocess(acts, min(latent_audio_len, n_ctx), meanpool, pool_frames_per_second, acts_rate)
+    length = min(latent_audio_len, n_ctx)
+    pool = _window_frames([length], meanpool, pool_frames_per_second, acts_rate, n_ctx)
+    acts = get_final_activations(z, x_cond, y_cond, top_prior, pool=pool)
+    acts = acts.squeeze(0).type(torch.float32)
+    if pool is not None:
+        return _postprocess_pooled(acts, length, pool[0], pool_frames_per_second)
+    return _postprocess(acts, length, meanpool, pool_frames_per_second, acts_rate)
 
 
 def get_acts_from_file(fpath, hps, vqvae, top_prior, meanpool=True, pool_frames_per_second=None):
@@ -195,8 +220,11 @@ def get_acts_from_audio_batch(audios: Sequence[np.ndarray], hps, vqvae, top_prio
     x = torch.from_numpy(np.stack(rows)).to(vqvae.device)
     z = vqvae.encode(x[:, :, None])[-1]
     x_cond, y_cond = get_cond(hps, top_prior)
-    acts = get_final_activations(z, x_cond, y_cond, top_prior)
     acts_rate = n_ctx / (expected / hps.sr)
+    pool = _window_frames(lens, meanpool, pool_frames_per_second, acts_rate, n_ctx)
+    acts = get_final_activations(z, x_cond, y_cond, top_prior, pool=pool)
+    if pool is not None:
+        return [_postprocess_pooled(acts[i], lens[i], pool[0], pool_frames_per_second) for i in range(len(audios))]
     return [_postprocess(acts[i], lens[i], meanpool, pool_frames_per_second, acts_rate) for i in range(len(audios))]
 
 
@@ -268,9 +296,8 @@ class WrappedAudioEncoder(torch.nn.Module):
         z = self.vqvae.encode_top(x)
         if self._cond is None:
             self._cond = get_cond(hps, self.top_prior)
-        acts = get_final_activations(z, self._cond[0], self._cond[1], self.top_prior)
         fl = self.frame_len
-        return ops.pool_window(acts, fl, hps.n_ctx // fl)
+        return get_final_activations(z, self._cond[0], self._cond[1], self.top_prior, pool=(fl, hps.n_ctx // fl))
 
 
 def _select_shard(paths, batch_size, batch_idx):

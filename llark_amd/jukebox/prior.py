@@ -54,6 +54,11 @@ DEFAULT_LN_PRED = True
 # launch (profiles/r05_cproj_bda_lnp_ab.txt): the co-resident workgroup hides only part of the epilogue and the transposed 32x32
 # accumulators reach the fp32 stream in 32-byte row pieces.  LLARK_PRIOR_CPROJ_BDA=1 takes it (same results to rounding).
 DEFAULT_CPROJ_BDA = False
+# forward(pool=(frame_len, frames)): the windowed mean that follows the stack is taken BEFORE the last block's second MLP product -- there is
+# no final LayerNorm and the mean is linear over rows, pool(h + g Wp2 + b2) = pool(h) + pool(g) Wp2 + b2 -- so that product runs on
+# n * frames rows instead of n * n_ctx (one pass of llark_pool_window_tail over h and the g planes replaces the product's full-M launch
+# and llark_pool_window).  LLARK_PRIOR_POOLED_TAIL=0 keeps the full product followed by llark_pool_window.  f16x2 only.
+DEFAULT_POOLED_TAIL = True
 
 
 class Labeller:
@@ -103,6 +108,8 @@ class PriorTransformer:
         self.ln_fold = bool(ln_fold) and precision == "f16x2"       # the lo8 tile has no folded epilogues
         self.ln_pred = self.ln_fold and os.environ.get("LLARK_PRIOR_LN_PRED", "1" if DEFAULT_LN_PRED else "0") != "0"
         self.cproj_bda = self.ln_fold and os.environ.get("LLARK_PRIOR_CPROJ_BDA", "1" if DEFAULT_CPROJ_BDA else "0") != "0"
+        self.fused_head = os.environ.get("LLARK_PRIOR_FUSED_HEAD", "1") != "0"      # 0: prior_embed + layernorm_split + ln_row_pred (bit-equal)
+        self.pooled_tail = precision == "f16x2" and os.environ.get("LLARK_PRIOR_POOLED_TAIL", "1" if DEFAULT_POOLED_TAIL else "0") != "0"
         self.width = hps.prior_width
         self.depth = hps.prior_depth if depth is None else depth
         dev = self.device
@@ -186,13 +193,15 @@ class PriorTransformer:
 
     # ---- one ResAttnBlock --------------------------------------------------------------------
     def layer_forward(self, h2: torch.Tensor, d: int, n: int, taps: Optional[dict] = None, fold_in: bool = False,
-                      fold_out: Optional[int] = None) -> None:
+                      fold_out: Optional[int] = None, skip_proj2: bool = False, head_done: bool = False) -> None:
         """h2: [M][W] fp32 residual stream, updated in place:  a = attn(ln_0(h)); h += a;
         m = mlp(ln_1(h)); h += m   (== upstream ``x + a + m`` evaluated left to right).
 
         ``fold_in`` / ``fold_out`` chain consecutive blocks in the folded-LayerNorm form (forward() sets them): fold_in = the
         workspace already holds the planes of h . ln_0.gamma and the row statistics (the previous block's fold_out);
-        fold_out = index of the block that follows, whose ln_0.gamma this block's last product multiplies in."""
+        fold_out = index of the block that follows, whose ln_0.gamma this block's last product multiplies in.
+        ``skip_proj2`` (f16x2, last block, no taps): stop after c_fc -- the g planes are left in the workspace for forward(pool=).
+        ``head_done`` (folded path, first block of a chain): ops.prior_head already wrote this block's ln_0 planes and the row predictions."""
         hps, L = self.hps, self.layers[d]
         rows = h2.shape[0]
         ws = self._workspace(rows)
@@ -200,8 +209,9 @@ class PriorTransformer:
         if self.precision == "lo8":
             return self._layer_forward_lo8(h2, L, d, n, ws, taps)
         if self._fold_rows and taps is None:
-            return self._layer_forward_fold(h2, L, d, n, ws, fold_in, fold_out)
-        assert not fold_in, "fold_in without the folded path"
+            return self._layer_forward_fold(h2, L, d, n, ws, fold_in, fold_out, skip_proj2, head_done)
+        assert not fold_in and not head_done, "fold_in / head_done without the folded path"
+        assert not (skip_proj2 and taps is not None), "skip_proj2 with taps"
         ops.layernorm_split(h2, L.ln0_g, L.ln0_b, 1e-5, ws["ln_hi"], ws["ln_lo"])
         ops.gemm16(ws["ln_hi"], ws["ln_lo"], L.w_attn, L.b_attn, 3 * S, ops.EPI_F32, c=ws["qkv"])
         ops.prior_attn(ws["qkv"], n, hps.n_ctx, S, hps.heads, hps.blocks, [1, 2, 3][d % 3], ws["att_hi"], ws["att_lo"])
@@ -217,20 +227,24 @@ class PriorTransformer:
         if taps is not None:
             taps["ln1"] = ws["ln_hi"].float() + ws["ln_lo"].float()
             taps["g"] = (ws["g_hi"].float() + ws["g_lo"].float())[:, :Mw]
+        if skip_proj2:
+            return
         ops.gemm16(ws["g_hi"], ws["g_lo"], L.w_proj2, L.b_proj2, W, ops.EPI_RESID, c=h2, resid=h2)
 
-    def _layer_forward_fold(self, h2, L, d: int, n: int, ws, fold_in: bool, fold_out: Optional[int]) -> None:
+    def _layer_forward_fold(self, h2, L, d: int, n: int, ws, fold_in: bool, fold_out: Optional[int], skip_proj2: bool = False,
+                            head_done: bool = False) -> None:
         """The block with its LayerNorms folded into the products around them (see DEFAULT_LN_FOLD).  Statistics are per-slice
         sums written by the producing epilogue and reduced in a fixed order: deterministic, batch-size independent."""
         hps = self.hps
         W, S, Mw = hps.prior_width, hps.n_state, hps.mlp_state
         rows, part, stat, pred = h2.shape[0], ws["ln_part"], ws["ln_stat"], ws["ln_pred"]
-        if pred is not None and not fold_in:
+        if pred is not None and not fold_in and not head_done:
             ops.ln_row_pred(h2, 1e-5, pred)                  # first block of a chain: predict from the stream as it stands
         if fold_in:
             ops.gemm16_ln(ws["ln_hi"], ws["ln_lo"], L.w_attn, L.bw_attn, 3 * S, ops.EPI_F32, L.gw_attn, ln_stat=stat, c=ws["qkv"])
         else:
-            ops.layernorm_split(h2, L.ln0_g, L.ln0_b, 1e-5, ws["ln_hi"], ws["ln_lo"])
+            if not head_done:
+                ops.layernorm_split(h2, L.ln0_g, L.ln0_b, 1e-5, ws["ln_hi"], ws["ln_lo"])
             ops.gemm16(ws["ln_hi"], ws["ln_lo"], L.w_attn, L.b_attn, 3 * S, ops.EPI_F32, c=ws["qkv"])
         ops.prior_attn(ws["qkv"], n, hps.n_ctx, S, hps.heads, hps.blocks, [1, 2, 3][d % 3], ws["att_hi"], ws["att_lo"])
         if self.cproj_bda:
@@ -246,6 +260,8 @@ class PriorTransformer:
         ops.gemm16_ln(ws["ln_hi"], ws["ln_lo"], L.w_fc, L.bw_fc, Mw, ops.EPI_QGELU_SPLIT, L.gw_fc, ln_stat=stat,
                       out_hi=ws["g_hi"], out_lo=ws["g_lo"])
         if fold_out is None:
+            if skip_proj2:
+                return
             ops.gemm16(ws["g_hi"], ws["g_lo"], L.w_proj2, L.b_proj2, W, ops.EPI_RESID, c=h2, resid=h2)
             return
         ops.gemm16_ln(ws["g_hi"], ws["g_lo"], L.w_proj2, L.b_proj2, W, ops.EPI_RESID, self.layers[fold_out].ln0_g, ln_part=part,
@@ -278,15 +294,23 @@ class PriorTransformer:
             taps["g"] = full(ws["g_hi"], ws["g_lo"], Mw)
         ops.gemm16_lo8(ws["g_hi"], ws["g_lo"], L.w_proj2, L.sw_proj2, L.b_proj2, W, ops.EPI_RESID, c=h2, resid=h2, w8=L.w8_proj2)
 
-    def embed(self, x: torch.Tensor, x_cond: torch.Tensor, y_cond: torch.Tensor) -> torch.Tensor:
+    def embed(self, x: torch.Tensor, x_cond: torch.Tensor, y_cond: torch.Tensor, head_ws=None) -> torch.Tensor:
+        """``head_ws`` (a workspace of the folded path): the one-pass head -- also block 0's ln_0 planes and the row predictions."""
         n, t = x.shape
         xc = x_cond.reshape(-1, self.width)[:t].contiguous()
         yc = y_cond.reshape(-1)[: self.width].contiguous()
+        if head_ws is not None:
+            L = self.layers[0]
+            return ops.prior_head(x.contiguous(), self.x_emb, self.pos_emb, xc, yc, L.ln0_g, L.ln0_b, 1e-5, head_ws["ln_hi"], head_ws["ln_lo"],
+                                  head_ws["ln_pred"])
         return ops.prior_embed(x.contiguous(), self.x_emb, self.pos_emb, xc, yc)
 
-    def forward(self, x, x_cond=None, y_cond=None, encoder_kv=None, fp16=False, depth: Optional[int] = None):
+    def forward(self, x, x_cond=None, y_cond=None, encoder_kv=None, fp16=False, depth: Optional[int] = None, pool=None):
         """``prior.forward(x, x_cond=, y_cond=, encoder_kv=None, fp16=False)`` with only_encode=True
-        (jukebox/main.py:105-108).  x: (N, n_ctx) int64 codes.  Returns (N, n_ctx, width) fp32."""
+        (jukebox/main.py:105-108).  x: (N, n_ctx) int64 codes.  Returns (N, n_ctx, width) fp32.
+
+        ``pool=(frame_len, frames)`` (NEW): returns the windowed mean (N, frames, width) of those activations instead
+        (``ops.pool_window``), taken before the last block's second MLP product where ``self.pooled_tail`` allows (see DEFAULT_POOLED_TAIL)."""
         if not self.only_encode:
             raise NotImplementedError("only the only_encode=True path of the prior is implemented (jukebox/main.py:105)")
         if encoder_kv is not None or fp16:
@@ -295,14 +319,33 @@ class PriorTransformer:
         x = x.to(self.device)
         n, t = x.shape
         assert t == self.hps.n_ctx, f"expected {self.hps.n_ctx} tokens, got {t}"
-        # x_cond / y_cond are the same for every clip (the reference keeps sample 0 only, main.py:95-96)
-        h = self.embed(x, x_cond[0:1] if x_cond.dim() == 3 else x_cond, y_cond)
-        h2 = h.view(n * t, self.width)
         nd = self.depth if depth is None else depth
         fold = self._workspace(n * t) is not None and self._fold_rows
+        # the folded chain's first block: embedding, ln_0 planes and row predictions in one pass over the rows (bit-equal to the three kernels)
+        head = fold and nd > 0 and self.fused_head and ops.prior_head_takes(self.width, self._ws["ln_hi"].stride(0))
+        # x_cond / y_cond are the same for every clip (the reference keeps sample 0 only, main.py:95-96)
+        h = self.embed(x, x_cond[0:1] if x_cond.dim() == 3 else x_cond, y_cond, self._ws if head else None)
+        h2 = h.view(n * t, self.width)
+        pooled = pool is not None and self.pooled_tail and nd > 0
         for d in range(nd):
-            self.layer_forward(h2, d, n, fold_in=fold and d > 0, fold_out=d + 1 if fold and d + 1 < nd else None)
-        return h
+            self.layer_forward(h2, d, n, fold_in=fold and d > 0, fold_out=d + 1 if fold and d + 1 < nd else None,
+                               skip_proj2=pooled and d == nd - 1, head_done=head and d == 0)
+        if pool is None:
+            return h
+        frame_len, frames = pool
+        if not pooled:
+            return ops.pool_window(h, frame_len, frames)
+        L, ws, W = self.layers[nd - 1], self._ws, self.width
+        out, pg_hi, pg_lo = ops.pool_window_tail(h, ws["g_hi"], ws["g_lo"], self.hps.mlp_state, frame_len, frames)
+        if ops.gemm16_batched_bias_takes(frames, W):
+            # one product per clip (m = frames) in one launch: a clip's rows do not depend on the batch it rides in
+            ops.gemm16_batched_bias(pg_hi, pg_lo, frames * pg_hi.stride(0), L.w_proj2, L.b_proj2, frames, W, out, W, frames * W, n,
+                                    resid=out, ldr=W, stride_r=frames * W)
+        else:
+            for i in range(n):
+                rows = slice(i * frames, (i + 1) * frames)
+                ops.gemm16(pg_hi[rows], pg_lo[rows], L.w_proj2, L.b_proj2, W, ops.EPI_RESID, c=out[rows], resid=out[rows])
+        return out.view(n, frames, W)
 
     __call__ = forward
 

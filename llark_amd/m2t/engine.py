@@ -49,11 +49,41 @@ def interleave_gate_up(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
     return torch.stack((gate.view(I // 32, 32, H), up.view(I // 32, 32, H)), dim=1).reshape(2 * I, H).contiguous()
 
 
+def _uniform_segments(audio_segments, h: torch.Tensor, S: int, hidden: int):
+    """(first batch row, start, clips, frames per clip, the (clips * frames, mm) fp32 matrix) when the segments are equal-length views of one
+    contiguous fp32 tensor on h's device, in consecutive batch rows, at the same start; else None (embed_splice then loops over them)."""
+    if len(audio_segments) < 2:
+        return None
+    b0, start, f0 = audio_segments[0]
+    if f0.dim() != 2 or f0.dtype != torch.float32 or f0.device != h.device or not f0.is_contiguous():
+        return None
+    F, mm = f0.shape
+    if F < 1 or start + 1 + F > S or not ops.gemm16_batched_bias_takes(F, hidden):
+        return None
+    base = f0.untyped_storage().data_ptr()
+    for i, (b, st, f) in enumerate(audio_segments):
+        if (b != b0 + i or st != start or f.shape != f0.shape or f.dtype != f0.dtype or f.device != f0.device or not f.is_contiguous()
+                or f.untyped_storage().data_ptr() != base or f.storage_offset() != f0.storage_offset() + i * F * mm):
+            return None
+    nb = len(audio_segments)
+    return b0, start, nb, F, f0.as_strided((nb * F, mm), (mm, 1))
+
+
 def embed_splice(ids: torch.Tensor, table: torch.Tensor, h: torch.Tensor, audio_segments, proj_w, proj_b, split: bool) -> None:
     """h[b * S + t] = table[ids[b, t]], then the projected frames of every (batch index, position of <audio_start>, frames fp32 (F, mm))
     overwrite rows start + 1 .. start + F of their sequence (the splice of m2t/models/llamav2.py:141-222).  Shared with HipMptEngine."""
     S = ids.shape[1]
     ops.embed_gather(ids.reshape(-1).contiguous(), table, h)
+    uni = _uniform_segments(audio_segments, h, S, table.shape[1])
+    if uni is not None:
+        # the clips' frames are one contiguous (nb * F, mm) matrix and the weight is shared: one split and one batched product whose
+        # per-clip C stride is a whole sequence of h -- every row bit-equal to the per-segment loop below (same kernel, same m)
+        assert proj_w is not None, "mm_projector weights not loaded"
+        b0, start, nb, F, flat = uni
+        a16, a16_lo = ops.split16(flat, torch.bfloat16, want_lo=split)
+        ops.gemm16_batched_bias(a16, a16_lo, F * a16.stride(0), proj_w, proj_b, F, table.shape[1], h[b0 * S + start + 1:], h.stride(0),
+                                S * h.stride(0), nb)
+        return
     for (b, start, frames) in audio_segments:
         assert proj_w is not None, "mm_projector weights not loaded"
         F = frames.shape[0]

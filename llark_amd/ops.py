@@ -332,6 +332,32 @@ def prior_embed(z, x_emb, pos_emb, x_cond, y_cond, out: Optional[torch.Tensor] =
     return out
 
 
+def prior_head_takes(width: int, ldo: int) -> bool:
+    """The shapes llark_prior_head takes (8 consecutive columns per lane, a wave's row sums within 64 KiB of LDS)."""
+    return width % 8 == 0 and width <= 8192 and ldo % 8 == 0
+
+
+def prior_head(z, x_emb, pos_emb, x_cond, y_cond, gamma, beta, eps: float, out_hi: torch.Tensor, out_lo: torch.Tensor,
+               pred: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`prior_embed` + :func:`layernorm_split` of the embedded rows (+ :func:`ln_row_pred` into ``pred``) in one pass, bit-equal to
+    that sequence (include/llark_hip.h, llark_prior_head).  Returns h [n][t][width]."""
+    n, t = z.shape
+    bins, width = x_emb.shape
+    assert pos_emb.shape == (t, width) and x_cond.numel() == t * width and y_cond.numel() == width
+    assert out_hi.shape == out_lo.shape and out_hi.shape[0] == n * t and out_hi.shape[1] >= width
+    if pred is not None:
+        assert pred.numel() >= 2 * n * t and pred.is_contiguous()
+    if out is None:
+        out = torch.empty((n, t, width), dtype=torch.float32, device=z.device)
+    check(_lib.lib().llark_prior_head(_dev(z, "z", torch.int64), n, t, width, bins, _dev(x_emb, "x_emb", torch.float32),
+                                      _dev(pos_emb, "pos_emb", torch.float32), _dev(x_cond, "x_cond", torch.float32),
+                                      _dev(y_cond, "y_cond", torch.float32), _dev(gamma, "gamma", torch.float32),
+                                      _dev(beta, "beta", torch.float32), float(eps), _dev(out, "h", torch.float32),
+                                      _dev(out_hi, "out_hi", torch.float16), _dev(out_lo, "out_lo", torch.float16), out_hi.stride(0),
+                                      _opt(pred, "pred", torch.float32), _stream()), "prior_head")
+    return out
+
+
 def layernorm_split(x: torch.Tensor, gamma, beta, eps: float, out_hi: torch.Tensor, out_lo: torch.Tensor) -> None:
     """x [rows][width] fp32 -> fp16 hi/lo planes [rows][ldo]."""
     rows, width = x.shape
@@ -386,6 +412,21 @@ def pool_window(h: torch.Tensor, frame_len: int, frames: int) -> torch.Tensor:
     check(_lib.lib().llark_pool_window(_dev(h, "h", torch.float32), n, t, width, frame_len, _dev(out, "out"), frames,
                                        _stream()), "pool_window")
     return out
+
+
+def pool_window_tail(h: torch.Tensor, g_hi: torch.Tensor, g_lo: torch.Tensor, gwidth: int, frame_len: int, frames: int):
+    """:func:`pool_window` of the stream h [n][t][width] and, in the same pass, of the fp16 planes g_hi / g_lo [n*t][ldg] (``gwidth``
+    valid columns) -> (pool_h [n*frames][width] fp32, pg_hi, pg_lo [n*frames][ldg]): include/llark_hip.h, llark_pool_window_tail."""
+    n, t, width = h.shape
+    ldg = g_hi.shape[1]
+    assert g_hi.shape == g_lo.shape == (n * t, ldg) and gwidth <= ldg
+    pool_h = torch.empty((n * frames, width), dtype=torch.float32, device=h.device)
+    pg_hi = torch.empty((n * frames, ldg), dtype=torch.float16, device=h.device)
+    pg_lo = torch.empty((n * frames, ldg), dtype=torch.float16, device=h.device)
+    check(_lib.lib().llark_pool_window_tail(_dev(h, "h", torch.float32), _dev(g_hi, "g_hi", torch.float16), _dev(g_lo, "g_lo", torch.float16),
+                                            n, t, width, gwidth, ldg, frame_len, frames, _dev(pool_h, "pool_h"), _dev(pg_hi, "pg_hi"),
+                                            _dev(pg_lo, "pg_lo"), _stream()), "pool_window_tail")
+    return pool_h, pg_hi, pg_lo
 
 
 def pool_mean(h: torch.Tensor, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1037,6 +1078,29 @@ def gemm16_batched(a: torch.Tensor, stride_a: int, lda: int, wt: torch.Tensor, s
     check(_lib.lib().llark_gemm16_batched(_DT[a.dtype], 0, EPI_F32, _dev(a, "a"), None, lda, stride_a, _dev(wt, "wt"), ldw,
                                           stride_w, m, n, kp, _dev(c, "c", torch.float32), ldc, stride_c, None, None, 0, 0,
                                           batch, _stream()), "gemm16_batched")
+
+
+def gemm16_batched_bias_takes(m: int, n: int) -> bool:
+    """Per-element shapes llark_gemm16_batched_bias takes: the per-tile kernels (never the persistent tiles of very large products)."""
+    return 1 <= m <= 1024 and n <= 16384
+
+
+def gemm16_batched_bias(a_hi: torch.Tensor, a_lo: Optional[torch.Tensor], stride_a: int, wt: torch.Tensor, bias: Optional[torch.Tensor],
+                        m: int, n: int, c: torch.Tensor, ldc: int, stride_c: int, batch: int, resid: Optional[torch.Tensor] = None,
+                        ldr: int = 0, stride_r: int = 0) -> None:
+    """c[b] [m][ldc] = (a_hi [+ a_lo])[b] [m][lda] . wt^T + bias (+ resid[b] [m][ldr]) for b < batch, element b at b * stride_a /
+    b * stride_c / b * stride_r (in elements): every element bit-equal to its own :func:`gemm16` call with EPI_F32 / EPI_RESID, whatever
+    the batch (include/llark_hip.h, llark_gemm16_batched_bias)."""
+    dtype = a_hi.dtype
+    assert dtype in (torch.float16, torch.bfloat16) and wt.dtype == dtype and wt.shape[0] >= n and a_hi.shape[1] >= wt.shape[1]
+    kp = wt.shape[1]
+    name = ("gemm_split_" if a_lo is not None else "gemm_") + ("f16" if dtype == torch.float16 else "bf16") + ("_skinny" if m <= 16 else "")
+    with _timed(name, 2.0 * batch * m * n * kp):
+        check(_lib.lib().llark_gemm16_batched_bias(_DT[dtype], int(a_lo is not None), EPI_F32 if resid is None else EPI_RESID, _dev(a_hi, "a_hi"),
+                                                   _opt(a_lo, "a_lo", dtype), a_hi.stride(0), stride_a, _dev(wt, "wt"), wt.stride(0), 0,
+                                                   _opt(bias, "bias", torch.float32), m, n, kp, _dev(c, "c", torch.float32, contiguous=False), ldc,
+                                                   stride_c, _opt(resid, "resid", torch.float32, contiguous=False), ldr, stride_r, None, None, 0, 0,
+                                                   batch, _stream()), "gemm16_batched_bias")
 
 
 def transpose16(src: torch.Tensor, ld_src: int, rows: int, cols: int, dst: torch.Tensor, ld_dst: int, batch: int = 1,
