@@ -527,7 +527,8 @@ int llark_attn_decode_bf16_dpos(const void* q, const void* k_cache, const void* 
                                 const void* k_cache_lo, const void* vt_cache_lo, int batch, int nh, int hd,
                                 const int* pos_dev, int smax, void* out, void* out_lo, llark_stream_t stream);
 /* CrossEntropyLoss on shifted logits (m2t/models/llamav2.py:316-325). logits fp32 [batch*s][ldl]; labels
- * int64 [batch][s]; row_loss scratch float[batch*s]; loss_out float[2] = {mean loss, counted rows}. */
+ * int64 [batch][s]; row_loss scratch float[batch*s]; loss_out float[2] = {mean loss, counted rows}.  A target outside
+ * [0, vocab) is treated like ignore_index: its row is not counted and gets a zero gradient (torch raises there). */
 int llark_cross_entropy_shifted(const float* logits, int ldl, int batch, int s, int vocab, const int64_t* labels,
                                 int64_t ignore_index, float* row_loss, float* loss_out, llark_stream_t stream);
 

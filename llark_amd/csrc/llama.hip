@@ -849,7 +849,7 @@ static int attn_decode(const AttnDecodeArgs& a) {
 
 // ------------------------------------------------------------------------------------------
 // Shifted cross-entropy (m2t/models/llamav2.py:316-325): row (b,s), s < S-1, predicts labels[b][s+1];
-// ignore_index rows are skipped; loss = mean over the counted rows (NaN when one of them is NaN, or when none counts).
+// ignore_index rows and rows whose target lies outside [0, vocab) are skipped; loss = mean over the counted rows (NaN when one of them is NaN, or when none counts).
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ logits, int ldl, int S, int vocab,
                                                       const long long* __restrict__ labels, long long ignore_index,

@@ -116,10 +116,12 @@ def test_attention_backward_matches_materialised_path():
         assert rel <= 5e-3, (name, rel)
 
 
-@pytest.mark.parametrize("B,S,nh,smax", [(2, 200, 2, 256), (2, 2048, 32, 2048), (2, 1000, 32, 1024)])
-def test_fused_glue_equals_the_separate_passes(B, S, nh, smax):
+@pytest.mark.parametrize("B,S,nh,smax,pos0", [(2, 200, 2, 256, 0), (2, 2048, 32, 2048, 0), (2, 1000, 32, 1024, 0), (2, 200, 2, 256, 24)],
+                         ids=["2-200-2-256", "2-2048-32-2048", "2-1000-32-1024", "2-200-2-256-pos24"])
+def test_fused_glue_equals_the_separate_passes(B, S, nh, smax, pos0):
     """llark_attn_backward_bf16_fused (round 6): dO read token-major + d(q | k | v) written as bf16 with the RoPE backward in the epilogues
-    == llark_split_heads16 + llark_attn_backward_bf16 + llark_rope_merge_bwd, bit for bit (same accumulators, same expressions)."""
+    == llark_split_heads16 + llark_attn_backward_bf16 + llark_rope_merge_bwd, bit for bit (same accumulators, same expressions); pos0 = 24:
+    the table rows of positions 24 .. 223 (llark_rope_merge_bwd itself is compared with float64 autograd in test_train_kernels_gpu.py)."""
     import torch
     from llark_amd import ops
     g = torch.Generator(device="cuda").manual_seed(12)
@@ -148,11 +150,11 @@ def test_fused_glue_equals_the_separate_passes(B, S, nh, smax):
     dsum = torch.empty(B * nh, S, dtype=f32, device="cuda")
     ops.attn_backward(q, kc, v_rm, dO, att, lse, dsum, B, S, nh, hd, dq, dk, dv)
     ref = torch.empty(B * S, 3 * H, dtype=bf, device="cuda")
-    ops.rope_merge_bwd(dq, dk, dv, cos_t, sin_t, B, S, nh, hd, 0, ref)
+    ops.rope_merge_bwd(dq, dk, dv, cos_t, sin_t, B, S, nh, hd, pos0, ref)
     # fused
     got = torch.full((B * S, 3 * H), 7.0, dtype=bf, device="cuda")
     dsum2 = torch.empty_like(dsum)
-    ops.attn_backward_fused(q, kc, v_rm, datt, att, lse, dsum2, B, S, nh, hd, cos_t, sin_t, 0, got)
+    ops.attn_backward_fused(q, kc, v_rm, datt, att, lse, dsum2, B, S, nh, hd, cos_t, sin_t, pos0, got)
     assert torch.equal(dsum, dsum2)
     assert torch.equal(got, ref), (got.float() - ref.float()).abs().max().item()
     assert ref.float().abs().max().item() > 0
