@@ -348,7 +348,8 @@ int llark_split16(int dtype, const float* x, int ldx, int rows, int width, void*
  * (m2t/models/llamav2.py:224-234) plus the embed_tokens gather (m2t/models/llamav2.py:124).
  * Residual stream fp32 [rows][hidden]; Linear inputs / q / k / v / probabilities bf16.
  * ------------------------------------------------------------------------------------------- */
-/* nn.Embedding gather: out[row] = table[ids[row]] (table_dtype LLARK_F16 / LLARK_BF16 / 2 = fp32). */
+/* nn.Embedding gather: out[row] = table[ids[row]] (table_dtype LLARK_F16 / LLARK_BF16 / 2 = fp32).  llark_embed_gather clamps ids
+ * to [0, vocab): a negative id reads row 0, an id >= vocab reads row vocab - 1 (torch raises there). */
 int llark_embed_gather(const int64_t* ids, int rows, const void* table, int table_dtype, int vocab, int width,
                        float* out, int ldo, llark_stream_t stream);
 /* LlamaRMSNorm -> bf16 (out_lo optional second plane with the rounding residual). */
@@ -362,6 +363,10 @@ int llark_rmsnorm_bf16(const float* x, int ldx, int rows, int width, const float
 int llark_rope_split_heads(const float* qkv, int batch, int s, int nh, int hd, int pos0, const float* cos_t,
                            const float* sin_t, int max_pos, void* q, void* k_cache, void* vt_cache, void* q_lo,
                            void* k_cache_lo, void* vt_cache_lo, int smax, llark_stream_t stream);
+/* smax % 8 == 0 for every attention entry point, prefill and decode, fused or not (LLARK_ERR_INVALID otherwise, before any launch):
+ * the kernels read V^T rows in 16-byte chunks of 8 keys.  Cache positions [total, round_up(total, 8)) are read by the decode forms
+ * and must hold finite values in every plane (stale rows of an earlier sequence are fine, NaN / Inf are not): they are multiplied by
+ * a zero probability (bf16 planes) or left out of the sum (hi + lo planes).  Positions >= round_up(total, 8) are never read. */
 /* causal attention over the cache: query i sees keys j <= past + i. out bf16 [batch*s][nh*hd]. */
 int llark_attn_prefill_bf16(const void* q, const void* k_cache, const void* vt_cache, const void* q_lo,
                             const void* k_cache_lo, const void* vt_cache_lo, int batch, int s, int nh, int hd, int past,

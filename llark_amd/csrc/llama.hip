@@ -774,7 +774,13 @@ __global__ __launch_bounds__(NW * 64, (NW >= 16 && UBT == 4) ? 7 : 1) void attn_
         for (int u = 0; u < UB; ++u) {
             const int c8 = cb + 8 * PARTS * u;
             if (c8 < tpad) {
-                if (vrl) {
+                if (vrl && c8 + 8 > total) {
+                    // the ragged last chunk of hi + lo planes: whatever the cache holds at total .. tpad-1 is finite per plane, but the
+                    // SUM of two stale planes need not be (0 * inf); those columns are left out instead of multiplied by p = 0
+#pragma unroll
+                    for (int e = 0; e < 8; ++e)
+                        if (c8 + e < total) acc = fmaf(sp[c8 + e], (float)vv[u][e] + (float)vl[u][e], acc);
+                } else if (vrl) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) acc = fmaf(sp[c8 + e], (float)vv[u][e] + (float)vl[u][e], acc);
                 } else {
@@ -813,7 +819,8 @@ static int attn_decode(const AttnDecodeArgs& a) {
     LLARK_REQUIRE(a.hd == 128, "%s: head_dim must be 128 (Llama-2), got %d", a.name, a.hd);
     LLARK_REQUIRE(!a.fused || ((a.k_cache_lo == nullptr) == (a.vt_cache_lo == nullptr) && (a.k_cache_lo == nullptr) == (a.out_lo == nullptr)),
                   "%s: give all lo planes (fp32-class mode) or none", a.name);
-    bool ok = a.batch > 0 && a.nh > 0 && (!a.fused || a.smax % 8 == 0);
+    // every form: the V pass reads 16-byte chunks of 8 keys up to round_up(total, 8) of V^T rows of length smax
+    bool ok = a.batch > 0 && a.nh > 0 && a.smax % 8 == 0;
     if (a.from == POS_HOST) ok = ok && a.total > 0 && a.total <= a.smax && (!a.fused || a.total <= a.max_pos);
     if (a.from == POS_DEV) ok = ok && (a.fused || a.smax > 0);
     if (a.from == POS_ROWS) ok = ok && a.smax > 0 && a.smax <= a.max_pos;

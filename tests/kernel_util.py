@@ -87,3 +87,14 @@ def out_slab(n, dtype, front=3, back=4):
     m = torch.zeros(size, dtype=torch.bool)
     m[front:front + n] = True
     return buf, m
+
+
+def check_frac(name, got, ref64, atol, r_torch):
+    """``check`` for outputs whose tolerance ``atol`` (numpy, per element) is a format term plus ``c * 2**-24 * B``: prints the kernel's
+    worst error as a fraction of that tolerance next to torch's float32 ratio ``r`` that set ``c``"""
+    got64 = got.detach().cpu().double()
+    err = (got64 - ref64.double()).abs().numpy()
+    pos = atol > 0
+    k = float((err[pos] / atol[pos]).max()) if pos.any() else 0.0
+    print(f"[ratio] {name}: kernel {k:.3g} of its tolerance, torch fp32 {r_torch:.3g} x 2^-24 B")
+    return report_close(name, got64.numpy(), ref64.double().numpy(), atol)
