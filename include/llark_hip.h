@@ -653,6 +653,43 @@ int llark_adamw_twins(void* p, const float* g, float* m, float* v, int n, int k,
                       float weight_decay, int step, float grad_scale, const double* grad_sumsq, float max_grad_norm, void* wfrag,
                       int rope_rows, void* wtfrag, llark_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * LoRA adapters on a frozen base (csrc/lora.hip; peft LoraLayer as configured by m2t/train.py:85-92: y = W x + (alpha / r) B (A x)).
+ * The low-rank products read one wide bf16 operand once for a 64-wide result: they are memory-bound and get kernels of their own
+ * (32-row tiles, the contraction split over the four waves of a workgroup) instead of 16 workgroups of the tiled GEMMs.
+ * Every entry point returns LLARK_ERR_UNSUPPORTED for a shape it does not take, before anything is launched.
+ * ------------------------------------------------------------------------------------------- */
+/* out[rows][ldo] (bf16, columns 0 .. rp_total - 1 of the pointer given: the caller may point into the tail of a wider buffer) =
+ * x[rows][lda] . m[rp_total][ldm]^T, bf16 operands, fp32 accumulation over k.  k % 16 == 0, rp_total % 64 == 0, rp_total <= 1024,
+ * lda / ldm / ldo % 8 == 0, every pointer 16-byte aligned, operands below 2^31 elements. */
+int llark_lora_down(const void* x, int lda, const void* m, int ldm, int rows, int k, int rp_total, void* out, int ldo,
+                    void* scratch, long long scratch_bytes, llark_stream_t stream);
+/* Bytes of scratch with which llark_lora_down splits the contraction over 2 or 4 workgroups per tile, when its (rows / 32) x
+ * (rp_total / 64) tiles alone would leave most of a 256-CU chip idle (0: the shape is not split).  fp32 partial sums, joined in a fixed
+ * order by a second small launch.  ``scratch`` NULL or smaller: one workgroup per tile, same result up to the fp32 summation order. */
+long long llark_lora_down_scratch_bytes(int rows, int k, int rp_total);
+/* Bytes of scratch llark_lora_dw needs for a shape (0 for a shape it does not take). */
+long long llark_lora_dw_scratch_bytes(int toks, int big, int rp);
+/* g[big][rp] fp32 (= | += when accumulate) scale * P^T . Q, contraction over the toks rows: P bf16 [toks][ldp] whose logical column
+ * i is the physical column (i / 32) * p_blk + i % 32 of the pointer given (p_blk = 32: a plain column window; 64: one half of the
+ * interleaved gate | up columns), Q bf16 [toks][ldq] (rp columns).  Columns r .. rp - 1 of g (the rank padding) take no gradient: they
+ * are written as zero (kept when accumulate).  sumsq (nullable, a double in device memory) += the sum of squares of every value
+ * stored to g (as llark_gemm16_t_sumsq).  Token-split partial sums go through `scratch` and a second small launch in a fixed order:
+ * no atomics on g, no waits between workgroups, results do not vary from run to run.
+ * big % 32 == 0, rp % 64 == 0, rp <= 256, 0 < r <= rp, p_blk % 32 == 0, p and q 4-byte aligned with even ldp / ldq (two adjacent
+ * columns are read as one word), g 16-byte aligned, scratch 16-byte aligned and of at least
+ * llark_lora_dw_scratch_bytes(toks, big, rp) bytes. */
+int llark_lora_dw(const void* p, int ldp, int p_blk, const void* q, int ldq, int toks, int big, int rp, int r, float scale,
+                  float* g, int accumulate, double* sumsq, void* scratch, long long scratch_bytes, llark_stream_t stream);
+/* bf16 operand copies of one fp32 adapter master src[rows][rp] (the A^T [K][rp] or B [N][rp] factor), times `scale`:
+ *   dst   [row_of(i)][ld_dst], columns 0 .. rp - 1 of the pointer given = scale * src[i][:]          (nullable)
+ *   dst_t [j][ld_t], column row_of(i) of the pointer given              = scale * src[i][j]          (nullable)
+ * with row_of(i) = (i / 32) * blk + i % 32 (blk = 32: identity; 64: the interleaved gate | up rows).  Only these elements are
+ * written: the rest of the stacked / block-diagonal operands (other adapters, zero blocks) is neither read nor written.
+ * rows % 32 == 0, rp % 32 == 0, blk % 32 == 0. */
+int llark_lora_refresh(const float* src, int rows, int rp, float scale, int blk, void* dst, int ld_dst, void* dst_t, int ld_t,
+                       llark_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,10 @@
 * ``save_total_limit`` (``train_llark.sh:42``) prunes old ``checkpoint-*`` folders; training resumes from the newest one
   when any exists (``m2t/train.py:257-260``).
 
+LoRA runs (``--lora_enable True``, m2t/train.py:264-273) write adapters instead of the model: ``checkpoint-<step>/`` then holds
+``adapter_model.bin`` (peft names, unpadded rank), ``adapter_config.json``, ``non_lora_trainables.bin`` (``mm_projector`` and
+``embed_tokens``, the trainable tensors that are not adapters) and ``trainer_state.pt`` -- and no ``pytorch_model.bin``.
+
 Added for exact resumption (the reference relies on HF Trainer's optimizer.pt / scheduler.pt / trainer_state.json): the
 fp32 AdamW moments and the step counter in ``trainer_state.pt`` (kernel layout, one flat tensor each).
 """
@@ -61,8 +65,16 @@ def save_checkpoint(trainer, output_dir: str, save_total_limit: Optional[int] = 
     folder = os.path.join(output_dir, f"checkpoint-{step}")
     tmp = folder + ".tmp"
     os.makedirs(tmp, exist_ok=True)
-    sd = {k: v.detach().cpu().contiguous() for k, v in trainer.eng.state_dict_hf().items()}
-    torch.save(sd, os.path.join(tmp, "pytorch_model.bin"))
+    lora = getattr(trainer, "lora", None)
+    if lora is not None:
+        from . import lora as LO
+
+        LO.save_adapter(tmp, trainer.get_adapters(), lora)
+        sd = {k: v.detach().cpu().contiguous() for k, v in adapter_state(trainer.eng.state_dict_hf()).items()}
+        torch.save(sd, os.path.join(tmp, LO.NON_LORA_TRAINABLES))
+    else:
+        sd = {k: v.detach().cpu().contiguous() for k, v in trainer.eng.state_dict_hf().items()}
+        torch.save(sd, os.path.join(tmp, "pytorch_model.bin"))
     torch.save({"step": step, "lr": trainer.lr, "betas": trainer.betas, "eps": trainer.eps, "weight_decay": trainer.wd,
                 "exp_avg": trainer.flat_m.cpu(), "exp_avg_sq": trainer.flat_v.cpu(),
                 "param_order": [n for n, _ in trainer.params]}, os.path.join(tmp, "trainer_state.pt"))
@@ -106,14 +118,36 @@ def copy_weights_into_engine(eng, sd: Dict[str, torch.Tensor], origin: str = "st
     eng.weights_changed_in_place()                            # fragment-major copies follow the new values
 
 
+def _load_lora_checkpoint(trainer, folder: str) -> None:
+    """Adapter factors + the trainable non-adapter tensors of a LoRA checkpoint; the frozen base keeps the values it was loaded with."""
+    from . import lora as LO
+
+    adapters, cfg = LO.load_adapter(folder)
+    if cfg.to_peft_dict() != trainer.lora.to_peft_dict():
+        raise ValueError(f"{folder}: adapter_config.json ({cfg}) differs from this run's LoRA configuration ({trainer.lora})")
+    trainer.set_adapters(adapters)
+    extra = torch.load(os.path.join(folder, LO.NON_LORA_TRAINABLES), map_location="cpu")
+    cur = adapter_state(trainer.eng.state_dict_hf())
+    missing = [k for k in cur if k not in extra]
+    if missing:
+        raise KeyError(f"{folder}: {LO.NON_LORA_TRAINABLES} lacks {missing[:3]}")
+    for k, dst in cur.items():
+        if dst.shape != extra[k].shape:
+            raise ValueError(f"{folder}: {k} has shape {tuple(extra[k].shape)}, engine expects {tuple(dst.shape)}")
+        dst.copy_(extra[k].to(device=dst.device, dtype=dst.dtype))
+
+
 def load_checkpoint(trainer, folder: str) -> int:
     """Restores weights (kernel layout, in place), AdamW moments and the step counter, then rebuilds the trainer's operands
     derived from the weights (twins, lm_head operands, per-step caches); returns the step."""
-    sd = torch.load(os.path.join(folder, "pytorch_model.bin"), map_location="cpu")
-    copy_weights_into_engine(trainer.eng, sd, origin=folder)
     st = torch.load(os.path.join(folder, "trainer_state.pt"), map_location="cpu")
     if st["param_order"] != [n for n, _ in trainer.params]:
         raise ValueError(f"{folder}: optimizer state was written for a different parameter table")
+    if getattr(trainer, "lora", None) is not None:
+        _load_lora_checkpoint(trainer, folder)
+    else:
+        sd = torch.load(os.path.join(folder, "pytorch_model.bin"), map_location="cpu")
+        copy_weights_into_engine(trainer.eng, sd, origin=folder)
     trainer.flat_m.copy_(st["exp_avg"])
     trainer.flat_v.copy_(st["exp_avg_sq"])
     trainer.step_count = int(st["step"])

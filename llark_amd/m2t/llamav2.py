@@ -210,6 +210,42 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
         self._engine = eng
         return eng
 
+    def load_lora_adapter(self, folder: str) -> None:
+        """Merges a saved LoRA adapter (``adapter_model.bin`` + ``adapter_config.json`` as a ``--lora_enable True`` run writes them,
+        plus ``non_lora_trainables.bin`` when present: m2t/train.py:264-273) into this module's weights, ``W + (alpha / r) B A`` like
+        peft's ``merge_and_unload``.  The engine is rebuilt from the merged weights on its next use: a LoRA-tuned model then generates
+        through the unchanged inference path."""
+        from . import lora as LO
+
+        adapters, cfg = LO.load_adapter(folder)
+        sd = self.state_dict()
+        merged = LO.merge_into_state_dict(sd, adapters, cfg)
+        extra_path = os.path.join(folder, LO.NON_LORA_TRAINABLES)
+        if os.path.exists(extra_path):
+            extra = torch.load(extra_path, map_location="cpu")
+            # the run added the audio tokens before it trained (initialize_audio_tokenizer): a base model loaded as it was published still
+            # has the smaller vocabulary and no projector.  Both are brought to the checkpoint's shapes here; lm_head keeps its trained rows.
+            emb = extra.get("model.embed_tokens.weight")
+            if emb is not None and emb.shape[0] != sd["model.embed_tokens.weight"].shape[0]:
+                if emb.shape[0] < sd["model.embed_tokens.weight"].shape[0]:
+                    raise ValueError(f"{extra_path}: embed_tokens has {emb.shape[0]} rows, fewer than the base model's "
+                                     f"{sd['model.embed_tokens.weight'].shape[0]}: not an adapter of this base model")
+                self.resize_token_embeddings(emb.shape[0])
+            if "model.mm_projector.weight" in extra and "model.mm_projector.weight" not in sd:
+                self.config.mm_hidden_size = extra["model.mm_projector.weight"].shape[1]
+                self.model.initialize_adapter_modules()
+                self.model.mm_projector.to(device=self.lm_head.weight.device, dtype=self.lm_head.weight.dtype)
+            sd = self.state_dict()
+            merged = {**sd, **{k: v for k, v in merged.items() if v.shape == sd[k].shape}}
+            for k, v in extra.items():
+                if k not in sd:
+                    raise KeyError(f"{extra_path}: unknown tensor {k}")
+                if v.shape != sd[k].shape:
+                    raise ValueError(f"{extra_path}: {k} has shape {tuple(v.shape)}, this model {tuple(sd[k].shape)}")
+                merged[k] = v.to(sd[k].device, sd[k].dtype)
+        self.load_state_dict(merged)
+        self._engine = None
+
     @property
     def engine(self) -> HipLlamaEngine:
         return self._engine if self._engine is not None else self.sync_engine()

@@ -3,8 +3,12 @@
 micro-batches, gradient accumulation, AdamW (lr 5e-5, weight decay 0), cosine schedule with 3 % linear warm-up,
 data-parallel gradient all-reduce over RCCL, bf16.
 
+Three recipes of the reference run here: full fine-tuning (the default), ``--freeze_backbone True`` (adapter-only pre-training,
+m2t/train.py:79,146-148) and ``--lora_enable True`` (m2t/train.py:82-99: rank-r adapters on q/k/v/o/gate/up/down_proj over a frozen
+base; ``llark_amd/m2t/lora.py``).
+
 Not reproduced (I/O + HF-Trainer glue out of scope): webdataset / GCS readers, wandb logging,
-HF ``TrainingArguments`` parsing, LoRA / bitsandbytes / FSDP options.  Batches are the dictionaries produced by
+HF ``TrainingArguments`` parsing, LoRA dropout / bias training, bitsandbytes / FSDP options.  Batches are the dictionaries produced by
 ``llark_amd.m2t.prompting.DataCollatorForSupervisedDataset`` (same keys as the reference's collator).
 """
 from __future__ import annotations
@@ -36,6 +40,22 @@ class TrainConfig:
     fuse_accumulation: bool = False             # run the accumulation micro-batches of a step as ONE pass when they share a shape and the engine
                                                 # holds them (loss normalised per micro-batch: the same gradient; 8 x 2048: 714 -> 685 ms, +60 GB)
     grad_comm: str = "bf16"                     # the reference's DDP buckets are bf16 (m2t/train.py:94-103 casts the model): 13.5 GB/step; "fp32" = 27 GB
+    freeze_backbone: bool = False               # m2t/train.py:79,146-148: only mm_projector and the audio-token embedding rows train
+    lora_enable: bool = False                   # m2t/train.py:82-99 (implies a frozen base)
+    lora_r: int = 64
+    lora_alpha: float = 16.0
+    lora_dropout: float = 0.0                   # the reference's default is 0.05; dropout is not built
+    lora_bias: str = "none"
+    seed: int = 42                              # adapter initialisation
+
+
+def lora_config_of(cfg) -> "Optional[LoraConfig]":
+    """The LoraConfig of a TrainConfig / parsed argument namespace (None when ``lora_enable`` is off)."""
+    from .lora import LoraConfig
+
+    if not getattr(cfg, "lora_enable", False):
+        return None
+    return LoraConfig(r=int(cfg.lora_r), alpha=float(cfg.lora_alpha), dropout=float(cfg.lora_dropout), bias=str(cfg.lora_bias))
 
 
 def lr_at(step: int, cfg: TrainConfig) -> float:
@@ -61,7 +81,8 @@ def train(engine, batches: Iterable[Dict], audio_cfg, cfg: TrainConfig = TrainCo
     tr = HipLlamaTrainer(engine, lr=cfg.learning_rate, betas=(cfg.adam_beta1, cfg.adam_beta2), eps=cfg.adam_epsilon,
                          weight_decay=cfg.weight_decay, embed_grad_tokens=toks,
                          grad_comm=torch.bfloat16 if cfg.grad_comm == "bf16" else torch.float32,
-                         gradient_checkpointing=cfg.gradient_checkpointing)
+                         gradient_checkpointing=cfg.gradient_checkpointing, freeze_backbone=cfg.freeze_backbone,
+                         lora=lora_config_of(cfg), lora_seed=cfg.seed)
     from . import checkpoint as CK
 
     if output_dir:
@@ -125,15 +146,22 @@ def train(engine, batches: Iterable[Dict], audio_cfg, cfg: TrainConfig = TrainCo
 def check_supported_recipe(args) -> None:
     """Flags whose reference meaning the native loop does NOT implement must not be swallowed: a run that silently
     trains something else than asked is worse than no run.
-      --freeze_backbone True  : m2t/train.py:150-151 ``model.requires_grad_(False)`` (adapter pre-training) -- the HIP
-                                trainer always updates the backbone;
+      --lora_dropout > 0      : adapter dropout is not built (the reference's default is 0.05: pass 0.0 explicitly);
+      --lora_bias != none     : biases do not train with the adapters;
+      --lora_r                : a multiple of 8 up to 256 (the kernels pad the rank to a multiple of 64);
       --tune_mm_mlp_adapter False: the reference then leaves EVERY embedding row and lm_head trainable
                                 (llamav2.py:395-419); the HIP trainer trains the two audio-token rows and freezes lm_head;
       --lr_scheduler_type     : only HF's cosine-with-warmup is implemented (train_llark.sh:35);
       --bf16 False            : the HIP training step is the bf16 flow."""
-    if getattr(args, "freeze_backbone", False):
-        raise NotImplementedError("--freeze_backbone True (adapter-only pre-training) is not implemented by the HIP trainer; "
-                                  "it would fine-tune all backbone weights")
+    if getattr(args, "lora_enable", False):
+        if float(getattr(args, "lora_dropout", 0.0)) != 0.0:
+            raise NotImplementedError(f"--lora_dropout {args.lora_dropout}: adapter dropout is not implemented; pass --lora_dropout 0.0 "
+                                      "(the reference's default is 0.05)")
+        if str(getattr(args, "lora_bias", "none")) != "none":
+            raise NotImplementedError(f"--lora_bias {args.lora_bias!r}: training biases with the adapters is not implemented (use 'none')")
+        r = int(getattr(args, "lora_r", 64))
+        if r <= 0 or r % 8 or r > 256:
+            raise NotImplementedError(f"--lora_r {r}: the rank must be a multiple of 8 between 8 and 256")
     if not getattr(args, "tune_mm_mlp_adapter", True):
         raise NotImplementedError("--tune_mm_mlp_adapter False (all embedding rows + lm_head trainable) is not implemented: the HIP "
                                   "trainer updates the audio-token embedding rows only and keeps lm_head frozen")
@@ -184,7 +212,13 @@ def main(argv=None):
     ap.add_argument("--gradient_checkpointing", type=boolean, default=False, help="train_llark.sh:25: recompute each decoder layer in the backward")
     ap.add_argument("--apply_task_sample_probs", type=boolean, default=False, help="m2t/arguments.py:68: weight shards by the task in their name")
     ap.add_argument("--task_sample_probs", default=None, help='JSON dict task -> probability (default: m2t/arguments.py:61-67)')
-    ap.add_argument("--freeze_backbone", type=boolean, default=False)
+    ap.add_argument("--freeze_backbone", type=boolean, default=False,
+                    help="m2t/train.py:79: train mm_projector and the audio-token embedding rows only")
+    ap.add_argument("--lora_enable", type=boolean, default=False, help="m2t/train.py:82-99: LoRA adapters on a frozen base")
+    ap.add_argument("--lora_r", type=int, default=64)
+    ap.add_argument("--lora_alpha", type=float, default=16.0)
+    ap.add_argument("--lora_dropout", type=float, default=0.0, help="only 0.0 is implemented (the reference's default is 0.05)")
+    ap.add_argument("--lora_bias", default="none", help="only 'none' is implemented")
     ap.add_argument("--lr_scheduler_type", default="cosine")
     ap.add_argument("--bf16", type=boolean, default=True)
     ap.add_argument("--max_grad_norm", type=float, default=1.0, help="HF TrainingArguments.max_grad_norm (gradient clipping; 0 = off)")
@@ -225,7 +259,9 @@ def main(argv=None):
     cfg = TrainConfig(learning_rate=args.learning_rate, weight_decay=args.weight_decay, warmup_ratio=args.warmup_ratio,
                       max_steps=args.max_steps, gradient_accumulation_steps=args.gradient_accumulation_steps, grad_comm=args.grad_comm,
                       gradient_checkpointing=args.gradient_checkpointing, max_grad_norm=args.max_grad_norm,
-                      fuse_accumulation=args.fuse_accumulation)
+                      fuse_accumulation=args.fuse_accumulation, freeze_backbone=args.freeze_backbone, lora_enable=args.lora_enable,
+                      lora_r=args.lora_r, lora_alpha=args.lora_alpha, lora_dropout=args.lora_dropout, lora_bias=args.lora_bias,
+                      seed=args.seed)
     task_probs = None
     if args.apply_task_sample_probs:
         import json as _json

@@ -1493,3 +1493,72 @@ def attn_decode_rope_chain(qkv: torch.Tensor, batch: int, nh: int, hd: int, pos:
         cos_t.shape[0], _dev(k_cache, "k_cache", bf), _dev(vt_cache, "vt_cache", bf), _opt(k_cache_lo, "k_cache_lo", bf),
         _opt(vt_cache_lo, "vt_cache_lo", bf), smax, _dev(out, "out", bf), _opt(out_lo, "out_lo", bf), None, done.data_ptr(), _stream()),
         "attn_decode_rope_chain")
+
+
+# ---- LoRA adapters on a frozen base (include/llark_hip.h: "LoRA adapters"; csrc/lora.hip) --------------------------------------------------
+ERR_UNSUPPORTED = -2                       # LLARK_ERR_UNSUPPORTED: the shape is outside what an entry point takes; nothing was launched
+_lora_scratch = {}
+_lora_down_scratch = {}
+
+
+def lora_down(x: torch.Tensor, m: torch.Tensor, out: torch.Tensor, k: Optional[int] = None) -> None:
+    """out[rows][:rp_total] = x[rows][:k] . m[rp_total][:k]^T (bf16, fp32 accumulation).  ``out`` may be a column window of a wider
+    buffer (only its rp_total columns are written); ``k`` defaults to m's width."""
+    bf = torch.bfloat16
+    rows, rp_total = x.shape[0], m.shape[0]
+    k = m.shape[1] if k is None else k
+    assert x.dtype == bf and m.dtype == bf and out.dtype == bf and x.stride(1) == 1 and m.stride(1) == 1 and out.stride(1) == 1
+    assert out.shape[0] == rows and out.shape[1] == rp_total and x.shape[1] >= k
+    need = int(_lib.lib().llark_lora_down_scratch_bytes(rows, k, rp_total))     # > 0: the contraction is split over workgroups as well
+    scratch = None
+    if need:
+        key = (torch.cuda.current_device(), _stream())
+        scratch = _lora_down_scratch.get(key)
+        if scratch is None or scratch.numel() * 4 < need:
+            scratch = _lora_down_scratch[key] = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=x.device)
+    with _timed("lora_down", 2.0 * rows * rp_total * k):
+        check(_lib.lib().llark_lora_down(_dev(x, "x", contiguous=False), x.stride(0), _dev(m, "m", contiguous=False), m.stride(0), rows, k,
+                                         rp_total, _dev(out, "out", contiguous=False), out.stride(0),
+                                         scratch.data_ptr() if scratch is not None else None, scratch.numel() * 4 if scratch is not None else 0,
+                                         _stream()), "lora_down")
+
+
+def lora_dw_scratch(toks: int, big: int, rp: int, device) -> torch.Tensor:
+    """Per-(device, stream) scratch of llark_lora_dw's token-split partial sums, grown on demand."""
+    need = int(_lib.lib().llark_lora_dw_scratch_bytes(int(toks), int(big), int(rp)))
+    key = (torch.cuda.current_device(), _stream())
+    t = _lora_scratch.get(key)
+    if t is None or t.numel() * 4 < need:
+        t = torch.empty((max(need, 16) + 3) // 4, dtype=torch.float32, device=device)
+        _lora_scratch[key] = t
+    return t
+
+
+def lora_dw(p: torch.Tensor, q: torch.Tensor, g: torch.Tensor, r: int, scale: float = 1.0, accumulate: bool = False,
+            sumsq: Optional[torch.Tensor] = None, p_blk: int = 32) -> None:
+    """g[big][rp] fp32 (= | +=) scale * P^T . Q over the tokens (rows of both).  ``p``: a bf16 [toks][>=...] view whose logical column i is
+    physical column (i // 32) * p_blk + i % 32 (a plain column window when p_blk == 32); ``q``: bf16 [toks][rp] view.  Rank-padding
+    columns r .. rp - 1 take no gradient.  ``sumsq`` (device double) += the sum of squares of what was stored."""
+    bf = torch.bfloat16
+    big, rp = g.shape
+    toks = p.shape[0]
+    assert p.dtype == bf and q.dtype == bf and g.dtype == torch.float32 and g.is_contiguous()
+    assert q.shape[0] == toks and q.shape[1] == rp and p.stride(1) == 1 and q.stride(1) == 1
+    scratch = lora_dw_scratch(toks, big, rp, g.device)
+    with _timed("lora_dw", 2.0 * toks * big * rp):
+        check(_lib.lib().llark_lora_dw(_dev(p, "p", contiguous=False), p.stride(0), int(p_blk), _dev(q, "q", contiguous=False), q.stride(0),
+                                       toks, big, rp, int(r), float(scale), _dev(g, "g"), int(accumulate),
+                                       _opt(sumsq, "sumsq", torch.float64), scratch.data_ptr(), scratch.numel() * 4, _stream()), "lora_dw")
+
+
+def lora_refresh(src: torch.Tensor, scale: float, dst: Optional[torch.Tensor], dst_t: Optional[torch.Tensor], blk: int = 32) -> None:
+    """bf16 operand copies of one fp32 adapter master ``src`` [rows][rp], times ``scale``: ``dst`` (a [>= row_of(rows)][rp] view) gets the
+    rows at row_of(i) = (i // 32) * blk + i % 32, ``dst_t`` (a [rp][>= row_of(rows)] view) the transpose.  Nothing else is touched."""
+    bf = torch.bfloat16
+    rows, rp = src.shape
+    assert src.dtype == torch.float32 and src.is_contiguous()
+    for t in (dst, dst_t):
+        assert t is None or (t.dtype == bf and t.stride(1) == 1)
+    check(_lib.lib().llark_lora_refresh(_dev(src, "src"), rows, rp, float(scale), int(blk),
+                                        _opt(dst, "dst", bf, contiguous=False), _ld(dst), _opt(dst_t, "dst_t", bf, contiguous=False), _ld(dst_t),
+                                        _stream()), "lora_refresh")
