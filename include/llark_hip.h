@@ -429,7 +429,12 @@ int llark_attn_prefill_bf16_lse(const void* q, const void* k_cache, const void* 
 /* Backward: q, dO, v_rm bf16 [batch*nh][s][128] (row-major); k_cache bf16 [batch*nh][smax][128]; o bf16 [batch*s][nh*128] = the
  * forward's out; lse from the forward; dsum fp32 [batch*nh][s] scratch.  Outputs dq, dk, dv fp32 [batch*nh][s][128] (before the RoPE
  * backward / head merge).  No transposed copies of any operand are needed (transposing LDS reads inside).
- * alibi_slopes (both calls): nullptr (Llama) or fp32 [nh] (MPT-1B trainer), the bias of llark_attn_prefill_bf16_alibi. */
+ * alibi_slopes (both calls): nullptr (Llama) or fp32 [nh] (MPT-1B trainer), the bias of llark_attn_prefill_bf16_alibi.
+ * The contract (tests/test_attn_bwd_kernels_gpu.py holds every output element to it): o and lse are used AS GIVEN, nothing of the
+ * forward is recomputed -- P_ij = exp(q_i.k_j / sqrt(hd) + slope_h (j - (s - 1)) - lse_i) for j <= i, else 0; D_i = sum_d dO_id o_id;
+ * dS = P (dO V^T - D); dv = P^T dO, dq = dS K / sqrt(hd), dk = dS^T Q / sqrt(hd), with P and dS each rounded to bf16 once.  dsum is an
+ * OUTPUT: it holds D = rowsum(dO * o) afterwards.  K-cache rows >= s are never read (nor any row >= s of q, v_rm, dO, lse).  dq, dk and
+ * dv must be 16-byte aligned (they are written as 4 floats per store).  No input is written; no atomics: launches are bit-reproducible. */
 int llark_attn_backward_bf16(const void* q, const void* k_cache, const void* v_rm, const void* dO, const void* o, const float* lse,
                              float* dsum, int batch, int s, int nh, int hd, int smax, float* dq, float* dk, float* dv,
                              const float* alibi_slopes, llark_stream_t stream);
@@ -608,7 +613,9 @@ int llark_attn_decode_rope_bf16_chain(const float* qkv, int batch, int nh, int h
  *     v_rm [batch][nh][s][128] (the attention backward's operand; no llark_transpose16 of the V^T cache);
  *   llark_attn_backward_bf16_fused: llark_attn_backward_bf16 that reads dO TOKEN-major ([batch*s][ld_do], head h at column 128 h: what the
  *     o_proj dX product leaves; no llark_split_heads16) and writes d(q | k | v) of the fused projection as bf16 dqkv [batch*s][3 nh 128] with
- *     the RoPE backward applied to the q and k parts (bit-equal to llark_rope_merge_bwd over the fp32 outputs of llark_attn_backward_bf16). */
+ *     the RoPE backward applied to the q and k parts (bit-equal to llark_rope_merge_bwd over the fp32 outputs of llark_attn_backward_bf16).
+ *     As there: o and lse are used as given, K-cache rows >= s are never read, dsum is an output holding rowsum(dO * o).  Of dO only the
+ *     columns [0, nh 128) of a row are read; dO must be 16-byte and dqkv 8-byte aligned, ld_do % 8 == 0; pos0 + s <= max_pos. */
 int llark_gemm16_fragw_rope_qkv_train(const void* a, int lda, const void* wfrag, int kp, int batch, int s, int nh, int hd, int pos0,
                                       const float* cos_t, const float* sin_t, int max_pos, void* q, void* k_cache, void* vt_cache, int smax,
                                       void* v_rm, llark_stream_t stream);

@@ -104,17 +104,20 @@ def prefill_case_id(shape, mode, alibi):
 # ---------------------------------------------------------------------------------------------------------------------
 # attention
 # ---------------------------------------------------------------------------------------------------------------------
-def attention(q, k, v, past, slopes=None, dtype=torch.float64, visible=None, total=None, bounds=True, want_p=False, budget=25e6):
+def attention(q, k, v, past, slopes=None, dtype=torch.float64, visible=None, total=None, bounds=True, want_p=False, budget=25e6, device=None):
     """Causal attention of q [N][S][128] over k / v [N][T][128]: query i sees key j <= past + i (``visible`` [S][T] bool overrides
     that).  ``slopes`` [N] adds slope_n * (j - (total - 1)) to the scaled scores (total = past + S).  Evaluated in ``dtype`` over
-    chunks of heads so that no more than ``budget`` scores are alive.  Returns out [N][S][128], lse [N][S] (natural log), and with
-    ``bounds`` B [N][S][128] and A [N][S]; with ``want_p`` the probabilities [N][S][T]."""
+    chunks of heads so that no more than ``budget`` scores are alive; ``device``: where the chunks are evaluated (operands and
+    results stay on the host).  Returns out [N][S][128], lse [N][S] (natural log), and with ``bounds`` B [N][S][128] and A [N][S];
+    with ``want_p`` the probabilities [N][S][T]."""
     N, S, _ = q.shape
     T = k.shape[1]
     total = past + S if total is None else total
     if visible is None:
         visible = torch.arange(T)[None, :] <= past + torch.arange(S)[:, None]
     rel = (torch.arange(T) - (total - 1)).to(dtype)
+    if device is not None:
+        visible, rel = visible.to(device), rel.to(device)
     out, lse = torch.empty((N, S, HD), dtype=dtype), torch.empty((N, S), dtype=dtype)
     Bb = torch.empty((N, S, HD), dtype=dtype) if bounds else None
     Aa = torch.empty((N, S), dtype=dtype) if bounds else None
@@ -122,11 +125,11 @@ def attention(q, k, v, past, slopes=None, dtype=torch.float64, visible=None, tot
     step = max(1, int(budget // (S * T)))
     for n0 in range(0, N, step):
         sl = slice(n0, min(N, n0 + step))
-        qc, kc, vc = q[sl].to(dtype), k[sl].to(dtype), v[sl].to(dtype)
+        qc, kc, vc = (t[sl].to(device=device, dtype=dtype) for t in (q, k, v))
         s = torch.matmul(qc, kc.transpose(1, 2)) * SCALE
         bias = None
         if slopes is not None:
-            bias = slopes[sl].to(dtype)[:, None, None] * rel[None, None, :]
+            bias = slopes[sl].to(device=device, dtype=dtype)[:, None, None] * rel[None, None, :]
             s = s + bias
         s = s.masked_fill(~visible[None], float("-inf"))
         m = s.amax(-1, keepdim=True)
