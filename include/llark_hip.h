@@ -622,6 +622,26 @@ int llark_gemm16_fragw_rope_qkv_train(const void* a, int lda, const void* wfrag,
 int llark_attn_backward_bf16_fused(const void* q, const void* k_cache, const void* v_rm, const void* dO, int ld_do, const void* o,
                                    const float* lse, float* dsum, int batch, int s, int nh, int hd, int smax, const float* cos_t,
                                    const float* sin_t, int pos0, int max_pos, void* dqkv, llark_stream_t stream);
+/* Variable-length (packed) forms of the training pair and its fused backward (csrc/llama.hip, csrc/attn_bwd.hip): a whole optimizer step of
+ * ragged sequences as ONE row stream with no padded sequence.  Layouts are those of the uniform calls with batch = 1 and s = s_total:
+ * q, v_rm, head-major dO [nh][s_total][128]; k_cache [nh][smax][128]; vt_cache [nh][128][smax]; out, o, token-major dO, dqkv [s_total][..];
+ * lse, dsum [nh][s_total].  seqs: DEVICE int32 [nseq][2] = (off_b, len_b): query i of sequence b is row off_b + i and sees keys
+ * off_b .. off_b + i, nothing else.  Llama only (no ALiBi), hd == 128.
+ *   Table contract: off_b % 8 == 0 (the forward reads V^T in 16-byte chunks of 8 keys, the rule behind smax % 8 == 0); len_b >= 1;
+ *   off_b + len_b <= s_total <= smax; ranges disjoint; max_len >= every len_b.  Rows that lie in no sequence are neither read nor written,
+ *   in any tensor.  The workgroups of an entry that breaks a rule return without touching memory: no table content can produce an access
+ *   outside rows [0, s_total).  (Overlapping ranges stay in bounds; their rows then hold either sequence's result.)
+ *   Scalars are checked before any launch (LLARK_ERR_INVALID): null pointer, hd != 128, 0 < max_len <= s_total <= smax, smax % 8 == 0,
+ *   max_len <= max_pos.  Results are bit-equal, sequence by sequence, to the uniform entry point called with batch = 1, s = len_b on that
+ *   sequence's rows; the fused backward's RoPE uses the position INSIDE the sequence (row off_b + i -> cos_t[i]).  No atomics. */
+int llark_attn_prefill_bf16_lse_varlen(const void* q, const void* k_cache, const void* vt_cache, const int* seqs, int nseq, int max_len,
+                                       int s_total, int nh, int hd, int smax, void* out, float* lse, llark_stream_t stream);
+int llark_attn_backward_bf16_varlen(const void* q, const void* k_cache, const void* v_rm, const void* dO, const void* o, const float* lse,
+                                    float* dsum, const int* seqs, int nseq, int max_len, int s_total, int nh, int hd, int smax, float* dq,
+                                    float* dk, float* dv, llark_stream_t stream);
+int llark_attn_backward_bf16_fused_varlen(const void* q, const void* k_cache, const void* v_rm, const void* dO, int ld_do, const void* o,
+                                          const float* lse, float* dsum, const int* seqs, int nseq, int max_len, int s_total, int nh, int hd,
+                                          int smax, const float* cos_t, const float* sin_t, int max_pos, void* dqkv, llark_stream_t stream);
 /* dW = dY^T . X without transposed copies of dY (csrc/gemm_bda.hip, round 6; torch autograd of nn.Linear: grad_weight = grad_output^T .
  * input, under WrappedLlamav2ForCausalLM.forward + loss.backward(), m2t/models/llamav2.py:259-337, m2t/train.py:53-277):
  *   llark_pack_frag_t16: src [kp][ld] 16-bit (row = contraction index: the token; column = feature) -> dst = the fragment-major copy of

@@ -104,6 +104,27 @@ __global__ __launch_bounds__(256) void attn_bwd_rowdot_kernel(const bf16_t* __re
     if (lane == 0) dsum[row] = v;
 }
 
+// The same for the sequences of a table (llark_attn_backward_bf16*_varlen; batch = 1, S = s_total in the layouts above): one wave per
+// (sequence, head, row below max_len); rows beyond the sequence's length, and rows of no sequence, are neither read nor written.
+__global__ __launch_bounds__(256) void attn_bwd_rowdot_varlen_kernel(const bf16_t* __restrict__ dO, const bf16_t* __restrict__ o,
+                                                                     float* __restrict__ dsum, int max_len, int nh, long rows, int ld_do,
+                                                                     const AttnSeqs<true> vl) {
+    const int lane = threadIdx.x & 63;
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);                  // = (b * nh + h) * max_len + i
+    if (r >= rows) return;
+    const long bh = r / max_len;
+    const int i = (int)(r - bh * max_len);
+    const int b = (int)(bh / nh), h = (int)(bh - (long)b * nh);
+    int off, len;
+    if (!attn_seq_of(vl, b, max_len, off, len) || i >= len) return;
+    const size_t s = (size_t)off + i, row = (size_t)h * vl.s_total + s;
+    const bf16_t* a = ld_do == 128 ? dO + row * 128 + lane * 2 : dO + s * (size_t)ld_do + h * 128 + lane * 2;
+    const bf16_t* c = o + s * (size_t)(nh * 128) + h * 128 + lane * 2;
+    float v = (float)a[0] * (float)c[0] + (float)a[1] * (float)c[1];
+    v = wave_sum(v);
+    if (lane == 0) dsum[row] = v;
+}
+
 // Round 6: the backward's layout glue folded into these kernels.  ld_do: see attn_bwd_rowdot_kernel.  dqkv != nullptr: instead of fp32
 // dq / dk / dv [bh][s][128] the epilogues write d(q | k | v) of the FUSED projection as bf16 [(b*S + s)][3 nh 128] with the RoPE backward
 // applied to the q and k parts (what llark_rope_merge_bwd did in a separate pass over 3 fp32 tensors: dx1 = dy1 c + dy2 s,
@@ -116,10 +137,10 @@ struct AttnBwdFused {
     int pos0;
 };
 
-// one row (query / key `pos_s` of sequence b, head h) of region 0 (q) / 1 (k) / 2 (v): acc[dt] = d = 16 dt + 4 g + r
-__device__ __forceinline__ void store_dqkv_row(const AttnBwdFused& f, const f32x4_t (&acc)[8], int region, int b, int h, int nh, int S, int pos_s, int g) {
+// one row (query / key `pos_s` of its sequence, head h; token row `row0 + pos_s` of dqkv) of region 0 (q) / 1 (k) / 2 (v): acc[dt] = d = 16 dt + 4 g + r
+__device__ __forceinline__ void store_dqkv_row(const AttnBwdFused& f, const f32x4_t (&acc)[8], int region, size_t row0, int h, int nh, int pos_s, int g) {
     typedef bf16_t bf4_t __attribute__((ext_vector_type(4)));
-    bf16_t* out = f.dqkv + ((size_t)b * S + pos_s) * (size_t)(3 * nh * 128) + (size_t)region * nh * 128 + h * 128 + 4 * g;
+    bf16_t* out = f.dqkv + (row0 + pos_s) * (size_t)(3 * nh * 128) + (size_t)region * nh * 128 + h * 128 + 4 * g;
     if (region == 2) {
 #pragma unroll
         for (int dt = 0; dt < 8; ++dt) {
@@ -181,13 +202,17 @@ constexpr float kLog2e = 1.4426950408889634f;
 // [128 d][16 keys] x NK in accumulators).  Per 64-query tile: S = Q K^T and dP = dO V^T with the queries as MFMA rows (A from LDS),
 // so P and dS leave the MFMA as "column = key, 4 rows = queries" -- the B-operand layout of dV^T = dO^T P and dK^T = Q^T dS
 // (A = the sequence-contiguous tiles in LDS).  Nothing goes through an LDS scratch.
-template <int NK, bool ALIBI>
+// VARLEN (llark_attn_backward_bf16*_varlen): S_arg = max_len sizes the grid, nbh = nseq * nh; the prologue reads the workgroup's sequence
+// (off, len) from the table, sets S = len and moves every base to the sequence's first row -- from there on the kernel is the batch = 1,
+// s = len call.  A workgroup whose pair index is beyond its sequence's tile count, or whose table entry is malformed, returns at once.
+template <int NK, bool ALIBI, bool VARLEN = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_bwd_dkv_kernel(const bf16_t* __restrict__ q,
                                                            const bf16_t* __restrict__ kc, const bf16_t* __restrict__ v_rm,
                                                            const bf16_t* __restrict__ dO,
                                                            const float* __restrict__ lse, const float* __restrict__ dsum,
-                                                           float* __restrict__ dk, float* __restrict__ dv, int S, int smax,
-                                                           int nbh, int nh, float scale, const float* __restrict__ alibi, const AttnBwdFused f, int paired) {
+                                                           float* __restrict__ dk, float* __restrict__ dv, int S_arg, int smax,
+                                                           int nbh, int nh, float scale, const float* __restrict__ alibi, const AttnBwdFused f, int paired,
+                                                           const AttnSeqs<VARLEN> vl) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // two LDS stages of DKV_STAGE bytes: Q [64 q][128 d] | dO [64][128] | log-sum-exp [64] | rowsum(dO * O) [64].  Tile qt+1 streams in
     // by LDS-DMA while tile qt is computed: one barrier per tile.  The products that contract over the queries (dV^T = dO^T P,
@@ -197,17 +222,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane >> 4, c = lane & 15;
-    const int nt = (S + 64 * NK - 1) / (64 * NK);
+    const int nt_grid = (S_arg + 64 * NK - 1) / (64 * NK);
     int pidx, bhid;
-    block_to_pair(paired ? (nt + 1) >> 1 : nt, nbh, pidx, bhid);                  // key tile 0 has the most query tiles: dispatched first
-    const size_t bh = (size_t)bhid;
-    const bf16_t* qb = q + bh * S * 128;
+    block_to_pair(paired ? (nt_grid + 1) >> 1 : nt_grid, nbh, pidx, bhid);        // key tile 0 has the most query tiles: dispatched first
+    int S = S_arg, nt = nt_grid;
+    size_t hrow0 = (size_t)bhid * S_arg;                                 // first row of the head-major planes (q, v_rm, dO, lse, dsum, dk, dv)
+    size_t krow0 = (size_t)bhid * smax;                                  // ... of the K cache
+    size_t trow0 = (size_t)(bhid / nh) * S_arg;                          // ... of the token-major tensors (dO, dqkv)
+    if constexpr (VARLEN) {
+        int off, len;
+        if (!attn_seq_of(vl, bhid / nh, S_arg, off, len)) return;
+        S = len;
+        nt = (S + 64 * NK - 1) / (64 * NK);
+        if (pidx >= (paired ? (nt + 1) >> 1 : nt)) return;
+        hrow0 = (size_t)(bhid % nh) * vl.s_total + off;
+        krow0 = (size_t)(bhid % nh) * smax + off;
+        trow0 = (size_t)off;
+    }
+    const bf16_t* qb = q + hrow0 * 128;
     const size_t ldo_ = (size_t)f.ld_do;                                 // 128: head-major dO; else token-major [(b*S + s)][ld_do], head at column 128 h
-    const bf16_t* dob = f.ld_do == 128 ? dO + bh * S * 128 : dO + (size_t)(bhid / nh) * S * ldo_ + (size_t)(bhid % nh) * 128;
-    const bf16_t* kb = kc + bh * (size_t)smax * 128;
-    const bf16_t* vb = v_rm + bh * S * 128;
-    const float* lb = lse + bh * S;
-    const float* db = dsum + bh * S;
+    const bf16_t* dob = f.ld_do == 128 ? dO + hrow0 * 128 : dO + trow0 * ldo_ + (size_t)(bhid % nh) * 128;
+    const bf16_t* kb = kc + krow0 * 128;
+    const bf16_t* vb = v_rm + hrow0 * 128;
+    const float* lb = lse + hrow0;
+    const float* db = dsum + hrow0;
     const float scale2 = scale * kLog2e;
     // ALiBi (MPT): the forward added slope_h * (key - (S - 1)) to the scaled scores; it has no gradient of its own
     const float slope2 = ALIBI ? alibi[bhid % nh] * kLog2e : 0.0f;     // (compile-time: the Llama instantiations carry no ALiBi arithmetic)
@@ -373,12 +411,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int dt = 0; dt < 8; ++dt) dka[u][dt] *= scale;          // the factor dS was formed without
             if (f.dqkv != nullptr) {
-                store_dqkv_row(f, dka[u], 1, bhid / nh, bhid % nh, nh, S, key, g);
-                store_dqkv_row(f, dva[u], 2, bhid / nh, bhid % nh, nh, S, key, g);
+                store_dqkv_row(f, dka[u], 1, trow0, bhid % nh, nh, key, g);
+                store_dqkv_row(f, dva[u], 2, trow0, bhid % nh, nh, key, g);
                 continue;
             }
-            float* ko = dk + (bh * S + key) * 128 + 4 * g;
-            float* vo = dv + (bh * S + key) * 128 + 4 * g;
+            float* ko = dk + (hrow0 + key) * 128 + 4 * g;
+            float* vo = dv + (hrow0 + key) * 128 + 4 * g;
 #pragma unroll
             for (int dt = 0; dt < 8; ++dt) {
                 *(f32x4_t*)(ko + dt * 16) = dka[u][dt];
@@ -391,12 +429,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // One workgroup per 64 NQ queries: wave wv owns queries q0 + 16 NQ wv .. as NQ sets of 16 (B operands Q, dO in registers, dQ^T in
 // accumulators).  Per 64-key tile: S^T = K Q^T and dP^T = V dO^T with the keys as MFMA rows (A from LDS), dS^T leaves the MFMA in
 // the B-operand layout of dQ^T = K^T dS^T (A = the sequence-contiguous K tile in LDS).
-template <int NQ, bool ALIBI>
+// VARLEN: as in the dK / dV kernel.
+template <int NQ, bool ALIBI, bool VARLEN = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_bwd_dq_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ kc,
                                                           const bf16_t* __restrict__ v_rm,
                                                           const bf16_t* __restrict__ dO, const float* __restrict__ lse,
-                                                          const float* __restrict__ dsum, float* __restrict__ dq, int S,
-                                                          int smax, int nbh, int nh, float scale, const float* __restrict__ alibi, const AttnBwdFused f, int paired) {
+                                                          const float* __restrict__ dsum, float* __restrict__ dq, int S_arg,
+                                                          int smax, int nbh, int nh, float scale, const float* __restrict__ alibi, const AttnBwdFused f, int paired,
+                                                          const AttnSeqs<VARLEN> vl) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // two LDS stages of 32 KiB: K [64 keys][128 d] | V [64][128]; tile kt+1 streams in by LDS-DMA while tile kt is computed.
     // dQ^T = K^T dS^T reads its A operand (row = d, contraction over the keys) from the row-major K tile through tr_frag.
@@ -404,15 +444,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane >> 4, c = lane & 15;
-    const int nt = (S + 64 * NQ - 1) / (64 * NQ);
+    const int nt_grid = (S_arg + 64 * NQ - 1) / (64 * NQ);
     int pidx, bhid;
-    block_to_pair(paired ? (nt + 1) >> 1 : nt, nbh, pidx, bhid);
-    const size_t bh = (size_t)bhid;
-    const bf16_t* qb = q + bh * S * 128;
+    block_to_pair(paired ? (nt_grid + 1) >> 1 : nt_grid, nbh, pidx, bhid);
+    int S = S_arg, nt = nt_grid;
+    size_t hrow0 = (size_t)bhid * S_arg;                                 // first rows: see the dK / dV kernel
+    size_t krow0 = (size_t)bhid * smax;
+    size_t trow0 = (size_t)(bhid / nh) * S_arg;
+    if constexpr (VARLEN) {
+        int off, len;
+        if (!attn_seq_of(vl, bhid / nh, S_arg, off, len)) return;
+        S = len;
+        nt = (S + 64 * NQ - 1) / (64 * NQ);
+        if (pidx >= (paired ? (nt + 1) >> 1 : nt)) return;
+        hrow0 = (size_t)(bhid % nh) * vl.s_total + off;
+        krow0 = (size_t)(bhid % nh) * smax + off;
+        trow0 = (size_t)off;
+    }
+    const bf16_t* qb = q + hrow0 * 128;
     const size_t ldo_ = (size_t)f.ld_do;                                 // 128: head-major dO; else token-major [(b*S + s)][ld_do], head at column 128 h
-    const bf16_t* dob = f.ld_do == 128 ? dO + bh * S * 128 : dO + (size_t)(bhid / nh) * S * ldo_ + (size_t)(bhid % nh) * 128;
-    const bf16_t* kb = kc + bh * (size_t)smax * 128;
-    const bf16_t* vb = v_rm + bh * S * 128;
+    const bf16_t* dob = f.ld_do == 128 ? dO + hrow0 * 128 : dO + trow0 * ldo_ + (size_t)(bhid % nh) * 128;
+    const bf16_t* kb = kc + krow0 * 128;
+    const bf16_t* vb = v_rm + hrow0 * 128;
     const float scale2 = scale * kLog2e;
     const float slope2 = ALIBI ? alibi[bhid % nh] * kLog2e : 0.0f;     // (compile-time: the Llama instantiations carry no ALiBi arithmetic)
 
@@ -434,8 +487,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 qf[u][ks] = *(const bf16x8_t*)(qb + (size_t)qr * 128 + ks * 32 + g * 8);
                 df[u][ks] = *(const bf16x8_t*)(dob + (size_t)qr * ldo_ + ks * 32 + g * 8);
             }
-            l2[u] = qi < S ? lse[bh * S + qi] * kLog2e : 0.0f;
-            dd[u] = qi < S ? dsum[bh * S + qi] : 0.0f;
+            l2[u] = qi < S ? lse[hrow0 + qi] * kLog2e : 0.0f;
+            dd[u] = qi < S ? dsum[hrow0 + qi] : 0.0f;
         }
         float nl2[NQ];                      // one fma per exponent: x = s scale2 - L log2 e; dS without its factor 1 / sqrt(d) (see the dK / dV kernel)
 #pragma unroll
@@ -552,10 +605,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int dt = 0; dt < 8; ++dt) dqa[u][dt] *= scale;          // the factor dS was formed without
             if (f.dqkv != nullptr) {
-                store_dqkv_row(f, dqa[u], 0, bhid / nh, bhid % nh, nh, S, qi, g);
+                store_dqkv_row(f, dqa[u], 0, trow0, bhid % nh, nh, qi, g);
                 continue;
             }
-            float* o = dq + (bh * S + qi) * 128 + 4 * g;
+            float* o = dq + (hrow0 + qi) * 128 + 4 * g;
 #pragma unroll
             for (int dt = 0; dt < 8; ++dt) *(f32x4_t*)(o + dt * 16) = dqa[u][dt];
         }
@@ -594,13 +647,64 @@ static int attn_backward_impl(const void* q, const void* k_cache, const void* v_
         (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<DKV_NK, AL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_kv);
         (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<DQ_NQ, AL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_q);
         attn_bwd_dkv_kernel<DKV_NK, AL><<<grid_kv, 256, lds_kv, st>>>((const bf16_t*)q, (const bf16_t*)k_cache, (const bf16_t*)v_rm, (const bf16_t*)dO, lse,
-                                                                   dsum, dk, dv, s, smax, nbh, nh, scale, alibi_slopes, f, pkv);
+                                                                   dsum, dk, dv, s, smax, nbh, nh, scale, alibi_slopes, f, pkv, AttnSeqs<false>{});
         attn_bwd_dq_kernel<DQ_NQ, AL><<<grid_q, 256, lds_q, st>>>((const bf16_t*)q, (const bf16_t*)k_cache, (const bf16_t*)v_rm, (const bf16_t*)dO, lse, dsum,
-                                                               dq, s, smax, nbh, nh, scale, alibi_slopes, f, pq);
+                                                               dq, s, smax, nbh, nh, scale, alibi_slopes, f, pq, AttnSeqs<false>{});
     };
     if (alibi_slopes) go(std::true_type{});
     else go(std::false_type{});
     return check_launch("attn_backward");
+}
+
+// The backward over the sequences of a table: the kernels above with their variable-length prologue.  The grid is sized for max_len --
+// np(max_len) * nseq * nh workgroups, those beyond their own sequence's tile count return -- and the tiles go in pairs when the SUMMED tile
+// count fills the chip as a uniform launch of that many tiles would.  The table lives on the device, so the sum is taken as
+// cdiv(s_total, 64): the ranges are disjoint, which puts the true sum between that and that + nseq.
+static int attn_backward_varlen_impl(const void* q, const void* k_cache, const void* v_rm, const void* dO, const void* o, const float* lse, float* dsum,
+                                     const int* seqs, int nseq, int max_len, int s_total, int nh, int smax, float* dq, float* dk, float* dv,
+                                     const AttnBwdFused& f, llark_stream_t stream) {
+    const float scale = (float)(1.0 / sqrt(128.0));
+    hipStream_t st = (hipStream_t)stream;
+    const AttnSeqs<true> vl = {seqs, s_total};
+    const long rows = (long)nseq * nh * max_len;
+    attn_bwd_rowdot_varlen_kernel<<<cdiv(rows, 4), 256, 0, st>>>((const bf16_t*)dO, (const bf16_t*)o, dsum, max_len, nh, rows, f.ld_do, vl);
+    const int nbh = nseq * nh;
+    const int nt = cdiv(max_len, 64);
+    const long wgs = (long)((cdiv(s_total, 64) + 1) / 2) * nh;
+    const int paired = nt >= 2 && (wgs >= 2048 || wgs == 512 || wgs == 1024);
+    const int grid = (paired ? (nt + 1) / 2 : nt) * nbh;
+    const int lds_kv = 2 * (32768 + 512), lds_q = 2 * 32768;
+    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<DKV_NK, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_kv);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<DQ_NQ, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_q);
+    attn_bwd_dkv_kernel<DKV_NK, false, true><<<grid, 256, lds_kv, st>>>((const bf16_t*)q, (const bf16_t*)k_cache, (const bf16_t*)v_rm, (const bf16_t*)dO, lse,
+                                                                        dsum, dk, dv, max_len, smax, nbh, nh, scale, nullptr, f, paired, vl);
+    attn_bwd_dq_kernel<DQ_NQ, false, true><<<grid, 256, lds_q, st>>>((const bf16_t*)q, (const bf16_t*)k_cache, (const bf16_t*)v_rm, (const bf16_t*)dO, lse, dsum,
+                                                                     dq, max_len, smax, nbh, nh, scale, nullptr, f, paired, vl);
+    return check_launch("attn_backward_varlen");
+}
+
+// llark_attn_backward_bf16 over the sequences of a device table seqs [nseq][2] = (off, len) (include/llark_hip.h): batch = 1, s = s_total.
+extern "C" int llark_attn_backward_bf16_varlen(const void* q, const void* k_cache, const void* v_rm, const void* dO, const void* o, const float* lse,
+                                               float* dsum, const int* seqs, int nseq, int max_len, int s_total, int nh, int hd, int smax, float* dq,
+                                               float* dk, float* dv, llark_stream_t stream) {
+    LLARK_REQUIRE(q && k_cache && v_rm && dO && o && lse && dsum && seqs && dq && dk && dv, "attn_backward_varlen: null pointer");
+    ATTN_VARLEN_REQUIRE_SHAPE("attn_backward_varlen");
+    AttnBwdFused f = {};
+    f.ld_do = 128;
+    return attn_backward_varlen_impl(q, k_cache, v_rm, dO, o, lse, dsum, seqs, nseq, max_len, s_total, nh, smax, dq, dk, dv, f, stream);
+}
+
+// llark_attn_backward_bf16_fused over the sequences of a table; the RoPE backward of row off + i uses position i (max_len <= max_pos).
+extern "C" int llark_attn_backward_bf16_fused_varlen(const void* q, const void* k_cache, const void* v_rm, const void* dO, int ld_do, const void* o,
+                                                     const float* lse, float* dsum, const int* seqs, int nseq, int max_len, int s_total, int nh, int hd,
+                                                     int smax, const float* cos_t, const float* sin_t, int max_pos, void* dqkv, llark_stream_t stream) {
+    LLARK_REQUIRE(q && k_cache && v_rm && dO && o && lse && dsum && seqs && cos_t && sin_t && dqkv, "attn_backward_fused_varlen: null pointer");
+    ATTN_VARLEN_REQUIRE_SHAPE("attn_backward_fused_varlen");
+    LLARK_REQUIRE(max_len <= max_pos, "attn_backward_fused_varlen: max_len %d beyond the RoPE table (%d positions)", max_len, max_pos);
+    LLARK_REQUIRE(ld_do >= nh * 128 && ld_do % 8 == 0 && ((uintptr_t)dO & 15) == 0 && ((uintptr_t)dqkv & 7) == 0, "attn_backward_fused_varlen: dO must be [s_total][ld_do >= nh*128], ld_do %% 8 == 0, 16-byte aligned");
+    AttnBwdFused f = {};
+    f.ld_do = ld_do; f.dqkv = (bf16_t*)dqkv; f.cos_t = cos_t; f.sin_t = sin_t; f.pos0 = 0;
+    return attn_backward_varlen_impl(q, k_cache, v_rm, dO, o, lse, dsum, seqs, nseq, max_len, s_total, nh, smax, nullptr, nullptr, nullptr, f, stream);
 }
 
 extern "C" int llark_attn_backward_bf16(const void* q, const void* k_cache, const void* v_rm, const void* dO, const void* o,

@@ -52,6 +52,13 @@ struct PerDeviceOnce {
         }                                        \
     } while (0)
 
+// the scalar arguments every variable-length attention entry point shares (hd, nseq, max_len, s_total, nh, smax in scope)
+#define ATTN_VARLEN_REQUIRE_SHAPE(name)                                                                                                    \
+    LLARK_REQUIRE(hd == 128, name ": head_dim must be 128 (Llama-2), got %d", hd);                                                          \
+    LLARK_REQUIRE(nseq > 0 && nh > 0 && max_len > 0 && max_len <= s_total && s_total <= smax && smax % 8 == 0 &&                            \
+                      (long)nseq * nh * max_len < (1l << 31) && (long)nh * smax < (1l << 31),                                               \
+                  name ": bad shape (need nseq, nh > 0, 0 < max_len <= s_total <= smax, smax %% 8 == 0)")
+
 // ---- in-launch hand-off between kernels that overlap across a launch boundary (round 6: decode; MI355X guide, Guideline 16) ---------
 // A consumer kernel may be resident (and already streaming the operands that do not depend on its producer) while the producer still runs on
 // another stream; it spins on the producer's arrival counter before touching what the producer writes.  Producer: every workgroup, after its
@@ -104,6 +111,23 @@ constexpr float CE_ROW_NOT_COUNTED = -1.0f;
 __device__ __forceinline__ bool ce_row_counted(float row_loss) { return row_loss != CE_ROW_NOT_COUNTED; }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Variable-length (packed) attention, the *_varlen entry points of llama.hip / attn_bwd.hip: the layouts of a batch = 1, s = s_total call,
+// cut into sequences by a device table seqs [nseq][2] = (off, len).  The uniform instantiations carry the empty form: no argument, no code.
+template <bool VARLEN>
+struct AttnSeqs {};
+template <>
+struct AttnSeqs<true> {
+    const int* seqs;
+    int s_total;
+};
+// (off, len) of sequence b.  false: the entry breaks the table's contract (off % 8 == 0, 1 <= len <= max_len, off + len <= s_total) and
+// the workgroup returns without touching memory -- whatever the table holds, no address outside rows [0, s_total) is ever formed.
+__device__ __forceinline__ bool attn_seq_of(const AttnSeqs<true>& v, int b, int max_len, int& off, int& len) {
+    off = __builtin_amdgcn_readfirstlane(v.seqs[2 * b]);
+    len = __builtin_amdgcn_readfirstlane(v.seqs[2 * b + 1]);
+    return off >= 0 && (off & 7) == 0 && len >= 1 && len <= max_len && len <= v.s_total && off <= v.s_total - len;
+}
 
 typedef _Float16 half_t;
 typedef _Float16 half4_t __attribute__((ext_vector_type(4)));

@@ -180,13 +180,18 @@ __device__ __forceinline__ int sub_row(int sub, int i) { return ((sub >> 1) << 5
 #ifndef ATTN_PREFILL_PF
 #define ATTN_PREFILL_PF 3         // plain bf16 operands: K / V^T fragments requested ahead of their products (see PF in the kernel)
 #endif
-template <bool SPLIT, int NQ, bool P2, bool ALIBI>
+// VARLEN (llark_attn_prefill_bf16_lse_varlen): the layouts of a batch = 1, s = s_total call cut into sequences by a device table.  S_arg =
+// max_len sizes the grid and nbh = nseq * nh; the prologue reads the workgroup's (off, len), sets S = len and moves every base to the
+// sequence's first row (a column offset for V^T: off % 8 == 0 keeps its 16-byte chunks aligned) -- from there on the kernel is the batch = 1,
+// s = len call.  A workgroup beyond its own sequence's block count, or with a malformed table entry, returns before touching memory.
+template <bool SPLIT, int NQ, bool P2, bool ALIBI, bool VARLEN = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NQ == 1 && !SPLIT) ? 3 : 2, (NQ == 1 && !SPLIT) ? 3 : 2))) void attn_prefill_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ kc,
                                                            const bf16_t* __restrict__ vtc, const bf16_t* __restrict__ q_lo,
                                                            const bf16_t* __restrict__ kc_lo, const bf16_t* __restrict__ vtc_lo,
                                                            bf16_t* __restrict__ out, bf16_t* __restrict__ out_lo,
-                                                           int S, int nh, int nbh, int past, int smax, float scale,
-                                                           const float* __restrict__ alibi_arg, float* __restrict__ lse, int paired) {
+                                                           int S_arg, int nh, int nbh, int past, int smax, float scale,
+                                                           const float* __restrict__ alibi_arg, float* __restrict__ lse, int paired,
+                                                           const AttnSeqs<VARLEN> vl) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const float* alibi = ALIBI ? alibi_arg : nullptr;               // compile-time: the Llama instantiations carry no ALiBi code
     // LDS: per stage K [64][128] 16 KiB + V^T [128][64] 16 KiB; !SPLIT two stages, SPLIT one stage + the lo planes
@@ -197,12 +202,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NQ == 1 &&
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane >> 4, c = lane & 15;
-    const int nt = (S + BQ - 1) / BQ;
+    const int nt_grid = (S_arg + BQ - 1) / BQ;
     // A workgroup takes TWO query blocks of one (batch, head): block nt - 1 - pidx (many keys) and then block pidx (few): every workgroup
     // does the same 2 nt + 2 key tiles of work -- with one causal block per workgroup the last-launched heads' long blocks ran alone
     // (53 % over the balanced time at 64 heads x 16 blocks, 13 % at 256 heads: scripts/sim_attn_order.py) -- and both blocks read the
     // same head's K / V (one L2 sees one head).
-    const int np = paired ? (nt + 1) >> 1 : nt;                     // (launcher: pairs only when they still fill the chip evenly)
+    const int np = paired ? (nt_grid + 1) >> 1 : nt_grid;           // (launcher: pairs only when they still fill the chip evenly)
     int pidx, bhid;
     {
         const int L = blockIdx.x;
@@ -215,16 +220,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NQ == 1 &&
         }
     }
     const int b = bhid / nh, h = bhid - b * nh;
+    int S = S_arg, nt = nt_grid;
+    size_t qrow0 = (size_t)bhid * S_arg;                            // first row of this (batch, head) in q and lse
+    size_t krow0 = (size_t)bhid * smax;                             // ... in the K cache
+    size_t vcol0 = (size_t)bhid * 128 * smax;                       // first element in the V^T cache
+    size_t orow0 = (size_t)b * S_arg;                               // first row of `out`
+    if constexpr (VARLEN) {
+        int off, len;
+        if (!attn_seq_of(vl, b, S_arg, off, len)) return;
+        S = len;
+        nt = (S + BQ - 1) / BQ;
+        if (pidx >= (paired ? (nt + 1) >> 1 : nt)) return;
+        qrow0 = (size_t)h * vl.s_total + off;
+        krow0 = (size_t)h * smax + off;
+        vcol0 = (size_t)h * 128 * smax + off;
+        orow0 = (size_t)off;
+    }
     const int total = past + S;                                     // keys available
     // ALiBi (MPT, m2t/llava/model/mpt/attention.py build_alibi_bias): additive bias slope_h * (key - (total - 1))
     const float slope2 = alibi ? alibi[h] * LOG2E : 0.0f;
     const float scale2 = scale * LOG2E;
-    const size_t bh = (size_t)bhid;
-    const bf16_t* qb = q + bh * S * 128;
-    const bf16_t* kb = kc + bh * (size_t)smax * 128;
-    const bf16_t* vb = vtc + bh * (size_t)128 * smax;
-    const bf16_t* kbl = SPLIT ? kc_lo + bh * (size_t)smax * 128 : nullptr;
-    const bf16_t* vbl = SPLIT ? vtc_lo + bh * (size_t)128 * smax : nullptr;
+    const bf16_t* qb = q + qrow0 * 128;
+    const bf16_t* kb = kc + krow0 * 128;
+    const bf16_t* vb = vtc + vcol0;
+    const bf16_t* kbl = SPLIT ? kc_lo + krow0 * 128 : nullptr;
+    const bf16_t* vbl = SPLIT ? vtc_lo + vcol0 : nullptr;
 
     // ---- staging.  !SPLIT: two LDS stages; tile kt+1 streams global -> LDS (LDS-DMA, no registers) while tile kt is computed,
     //      one barrier per tile.  The DMA image is lane-linear, so lane i of the instruction that covers rows 4j..4j+3 of K
@@ -331,7 +351,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NQ == 1 &&
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 qf[u][ks] = *(const bf16x8_t*)(qb + (size_t)qr * 128 + ks * 32 + g * 8);
-                if (SPLIT) ql[u][ks] = *(const bf16x8_t*)(q_lo + bh * S * 128 + (size_t)qr * 128 + ks * 32 + g * 8);
+                if (SPLIT) ql[u][ks] = *(const bf16x8_t*)(q_lo + qrow0 * 128 + (size_t)qr * 128 + ks * 32 + g * 8);
             }
         }
         f32x4_t o[NQ][8];                                               // O^T: d = dt*16 + 4g + r, query c
@@ -573,8 +593,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NQ == 1 &&
             if (qi >= S) continue;
             const float inv = l_run[u] > 0.0f ? 1.0f / l_run[u] : 0.0f;
             // natural-log log-sum-exp of the scaled, masked scores (attn_bwd.hip recomputes P from it)
-            if (lse && g == 0) lse[bh * S + qi] = (m_run[u] + log2f(l_run[u])) * 0.6931471805599453f;
-            const size_t dst = ((size_t)b * S + qi) * (size_t)(nh * 128) + h * 128;
+            if (lse && g == 0) lse[qrow0 + qi] = (m_run[u] + log2f(l_run[u])) * 0.6931471805599453f;
+            const size_t dst = (orow0 + qi) * (size_t)(nh * 128) + h * 128;
 #pragma unroll
             for (int dt = 0; dt < 8; ++dt) {
                 bf16x4_t hi4, lo4;
@@ -610,7 +630,7 @@ static void launch_attn_prefill(hipStream_t st, const bf16_t* q, const bf16_t* k
             static PerDeviceOnce once;                              // per (instantiation, device): the attribute belongs to the device's function object
             if (once.first()) (void)hipFuncSetAttribute((const void*)attn_prefill_kernel<SPLIT, NQ, P2, AL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
             attn_prefill_kernel<SPLIT, NQ, P2, AL><<<(pr ? (nt + 1) / 2 : nt) * nbh, 256, lds, st>>>(q, kc, vtc, q_lo, kc_lo, vtc_lo, out, out_lo, s, nh, nbh, past,
-                                                                                           smax, scale, alibi, lse, pr);
+                                                                                           smax, scale, alibi, lse, pr, AttnSeqs<false>{});
         };
         // (hi+lo planes: two query sets per wave do not fit 256 registers)
         if (!SPLIT && (long)cdiv(s, 128) * nbh >= 1024) run(std::integral_constant<int, SPLIT ? 1 : 2>{});
@@ -1087,6 +1107,26 @@ extern "C" int llark_attn_prefill_bf16_lse(const void* q, const void* k_cache, c
     launch_attn_prefill<false, false>((hipStream_t)stream, (const bf16_t*)q, (const bf16_t*)k_cache, (const bf16_t*)vt_cache, nullptr,
                                       nullptr, nullptr, (bf16_t*)out, nullptr, batch, s, nh, 0, smax, scale, alibi_slopes, lse);
     return check_launch("attn_prefill_lse");
+}
+
+// llark_attn_prefill_bf16_lse over the sequences of a device table seqs [nseq][2] = (off, len) (include/llark_hip.h): batch = 1, s = s_total,
+// the 64-query instantiation.  The grid is sized for max_len: np(max_len) * nseq * nh workgroups, those beyond their own sequence's block
+// count return.  Blocks go in pairs when the summed block count -- taken as cdiv(s_total, 64): the table lives on the device, the ranges are
+// disjoint, so the true sum lies between that and that + nseq -- fills the chip as a uniform launch of that many blocks would.
+extern "C" int llark_attn_prefill_bf16_lse_varlen(const void* q, const void* k_cache, const void* vt_cache, const int* seqs, int nseq, int max_len,
+                                                  int s_total, int nh, int hd, int smax, void* out, float* lse, llark_stream_t stream) {
+    LLARK_REQUIRE(q && k_cache && vt_cache && seqs && out && lse, "attn_prefill_lse_varlen: null pointer");
+    ATTN_VARLEN_REQUIRE_SHAPE("attn_prefill_lse_varlen");
+    const int lds = 65536, nbh = nseq * nh, nt = cdiv(max_len, 64);
+    const long wgs = (long)((cdiv(s_total, 64) + 1) / 2) * nh;
+    const int pr = nt >= 2 && (wgs >= 2048 || wgs == 512 || wgs == 1024);
+    static PerDeviceOnce once;
+    if (once.first()) (void)hipFuncSetAttribute((const void*)attn_prefill_kernel<false, 1, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    const AttnSeqs<true> vl = {seqs, s_total};
+    attn_prefill_kernel<false, 1, false, false, true><<<(pr ? (nt + 1) / 2 : nt) * nbh, 256, lds, (hipStream_t)stream>>>(
+        (const bf16_t*)q, (const bf16_t*)k_cache, (const bf16_t*)vt_cache, nullptr, nullptr, nullptr, (bf16_t*)out, nullptr, max_len, nh, nbh, 0, smax,
+        (float)(1.0 / sqrt((double)hd)), nullptr, lse, pr, vl);
+    return check_launch("attn_prefill_lse_varlen");
 }
 
 extern "C" int llark_attn_prefill_bf16(const void* q, const void* k_cache, const void* vt_cache, const void* q_lo,

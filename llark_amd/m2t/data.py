@@ -22,7 +22,8 @@ import pickle
 import random
 import re
 import tarfile
-from typing import Any, Dict, Iterable, Iterator, List, Optional, Sequence
+from dataclasses import dataclass
+from typing import Any, Dict, Iterable, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -199,3 +200,104 @@ def micro_batches(train_data_path: str, tokenizer, multimodal_cfg: Dict[str, Any
                 yield collate(pending)
                 pending = []
         epoch += 1
+
+
+# ---- packed ragged step (``--pack_sequences``): a whole optimizer step as ONE row stream ------------------------------------------------
+IGNORE_INDEX = -100
+PACK_ALIGN = 8               # every sequence starts at a multiple of 8 rows (the attention forward reads V^T in chunks of 8 keys)
+
+
+@dataclass
+class PackedStep:
+    """The micro-batches of one optimizer step as a single stream of ``s_total`` rows with no padded sequence: sequence b occupies rows
+    ``off_b .. off_b + len_b - 1`` (``len_b`` = its token count rounded up to PACK_ALIGN with ``pad_id`` / label -100; the pad rows follow
+    their own sequence's tokens in the causal order, get no loss and so contribute exactly zero to every gradient)."""
+    ids: torch.Tensor                          # int64 [s_total]
+    labels: torch.Tensor                       # int64 [s_total]: first row of every sequence and every pad row are -100 (no row predicts across a boundary)
+    seqs: List[Tuple[int, int]]                # (off_b, len_b), off_b % 8 == 0, contiguous: no row of the stream lies outside a sequence
+    groups: List[Tuple[int, int]]              # [r0, r1) of each micro-batch: the loss is the mean over the micro-batches of each one's token mean
+    segments: list                             # (sequence index, position of <audio_start> inside the sequence, frames)
+    positions: torch.Tensor                    # int64 [s_total]: RoPE position of a row = its index inside its sequence
+    tokens: List[int]                          # unpadded length of every sequence
+
+    @property
+    def s_total(self) -> int:
+        return int(self.ids.numel())
+
+    @property
+    def max_len(self) -> int:
+        return max(n for _, n in self.seqs)
+
+
+def pack_sequences(seqs: Sequence[torch.Tensor], labels: Sequence[torch.Tensor], groups: Sequence[int], segments=(), pad_id: int = 0) -> PackedStep:
+    """Pure host function.  ``seqs`` / ``labels``: 1-D id / label tensors of any (equal per pair) lengths; ``groups``: how many consecutive
+    sequences form each micro-batch; ``segments``: (sequence index, start, frames) with ``start`` inside the sequence."""
+    if len(seqs) != len(labels) or sum(int(g) for g in groups) != len(seqs) or any(int(g) < 1 for g in groups):
+        raise ValueError(f"pack_sequences: {len(seqs)} sequences, {len(labels)} label rows, groups {list(groups)} do not match")
+    ids_out, lab_out, pos_out, table, tokens = [], [], [], [], []
+    off = 0
+    for b, (s, l) in enumerate(zip(seqs, labels)):
+        s, l = s.detach().cpu().reshape(-1).long(), l.detach().cpu().reshape(-1).long()
+        n = int(s.numel())
+        if n < 1 or int(l.numel()) != n:
+            raise ValueError(f"pack_sequences: sequence {b} has {n} tokens and {int(l.numel())} labels")
+        ln = -(-n // PACK_ALIGN) * PACK_ALIGN
+        ids_b = torch.full((ln,), int(pad_id), dtype=torch.long)
+        lab_b = torch.full((ln,), IGNORE_INDEX, dtype=torch.long)
+        ids_b[:n] = s
+        lab_b[1:n] = l[1:]                                   # a sequence's first label is never a target (the loss is shifted)
+        ids_out.append(ids_b)
+        lab_out.append(lab_b)
+        pos_out.append(torch.arange(ln, dtype=torch.long))
+        table.append((off, ln))
+        tokens.append(n)
+        off += ln
+    ranges, b0 = [], 0
+    for g in groups:
+        b1 = b0 + int(g)
+        ranges.append((table[b0][0], table[b1 - 1][0] + table[b1 - 1][1]))
+        b0 = b1
+    segs = []
+    for (b, start, frames) in segments:
+        b, start = int(b), int(start)
+        if not (0 <= b < len(table)) or start < 0 or start + 1 + int(frames.shape[0]) > tokens[b]:
+            raise ValueError(f"pack_sequences: audio segment (sequence {b}, start {start}, {int(frames.shape[0])} frames) lies outside its sequence")
+        segs.append((b, start, frames))
+    return PackedStep(torch.cat(ids_out), torch.cat(lab_out), table, ranges, segs, torch.cat(pos_out), tokens)
+
+
+def plan_packed_step(micro_batches_: Sequence[Dict[str, Any]], audio_cfg, pad_id: int) -> PackedStep:
+    """The collated micro-batches of one optimizer step (``input_ids``, ``labels``, optional ``attention_mask`` / ``audio_encodings``) ->
+    one :class:`PackedStep`.  Right padding is stripped with ``attention_mask``; without one, a trailing run of positions whose label is
+    -100 and whose id is ``pad_id`` counts as padding.  A micro-batch none of whose rows keeps a token is refused."""
+    from .llamav2 import plan_audio_splice
+
+    seqs, labels, groups, segments = [], [], [], []
+    for k, mb in enumerate(micro_batches_):
+        ids, lab = mb["input_ids"].detach().cpu(), mb["labels"].detach().cpu()
+        mask = mb.get("attention_mask")
+        if mask is not None:
+            keep = mask.detach().cpu().bool()
+        else:
+            keep = ~((ids == pad_id) & (lab == IGNORE_INDEX))
+        lengths = []
+        for b in range(ids.shape[0]):
+            nz = keep[b].nonzero().reshape(-1)
+            lengths.append(int(nz[-1]) + 1 if nz.numel() else 0)
+        if not any(lengths):
+            raise ValueError(f"plan_packed_step: micro-batch {k} has no token left after its padding is stripped")
+        feats = mb.get("audio_encodings")
+        segs = plan_audio_splice(ids, feats, audio_cfg, False) if feats is not None else []
+        index = {}
+        for b, n in enumerate(lengths):
+            if n == 0:                                        # an all-padding row of a micro-batch that has others: nothing to learn from
+                continue
+            index[b] = len(seqs)
+            seqs.append(ids[b, :n])
+            labels.append(lab[b, :n])
+        groups.append(len(index))
+        for (b, start, frames) in segs:
+            if b not in index:
+                raise ValueError(f"plan_packed_step: micro-batch {k}, row {b}: audio in a row that is all padding")
+            segments.append((index[b], start, frames))
+    return pack_sequences(seqs, labels, groups, segments, pad_id)

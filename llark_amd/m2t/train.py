@@ -39,6 +39,8 @@ class TrainConfig:
     max_grad_norm: float = 1.0                  # transformers TrainingArguments default (clip_grad_norm_ in Trainer's step); not set by train_llark.sh
     fuse_accumulation: bool = False             # run the accumulation micro-batches of a step as ONE pass when they share a shape and the engine
                                                 # holds them (loss normalised per micro-batch: the same gradient; 8 x 2048: 714 -> 685 ms, +60 GB)
+    pack_sequences: bool = False                # run the step's ragged micro-batches as ONE packed stream: no pad rows, one pass over the weights
+                                                # (variable-length attention; loss normalised per micro-batch: the same gradient).  Llama only
     grad_comm: str = "bf16"                     # the reference's DDP buckets are bf16 (m2t/train.py:94-103 casts the model): 13.5 GB/step; "fp32" = 27 GB
     freeze_backbone: bool = False               # m2t/train.py:79,146-148: only mm_projector and the audio-token embedding rows train
     lora_enable: bool = False                   # m2t/train.py:82-99 (implies a frozen base)
@@ -77,6 +79,12 @@ def train(engine, batches: Iterable[Dict], audio_cfg, cfg: TrainConfig = TrainCo
     written into every checkpoint folder so that ``from_pretrained`` / ``load_pretrained_model`` can open it.
     ``batches`` may be a callable ``skip_micro_batches -> iterable``: it is then called with the number of micro-batches
     the resumed run has already consumed (``step * gradient_accumulation_steps``) so the data stream continues."""
+    if cfg.pack_sequences:
+        from .engine import HipLlamaEngine
+
+        if not isinstance(engine, HipLlamaEngine):
+            raise NotImplementedError(f"--pack_sequences: packing is built for the Llama training step only, not for {type(engine).__name__} "
+                                      "(ALiBi attention has no variable-length form)")
     toks = [t for t in (audio_cfg.audio_start_token, audio_cfg.audio_end_token) if isinstance(t, int)]
     tr = HipLlamaTrainer(engine, lr=cfg.learning_rate, betas=(cfg.adam_beta1, cfg.adam_beta2), eps=cfg.adam_epsilon,
                          weight_decay=cfg.weight_decay, embed_grad_tokens=toks,
@@ -100,7 +108,40 @@ def train(engine, batches: Iterable[Dict], audio_cfg, cfg: TrainConfig = TrainCo
                                    last_micro_batch=last and cfg.max_grad_norm > 0)
         return float(loss.item()) / accum
 
+    pad_id = getattr(tokenizer, "pad_token_id", None)
+    pad_id = 0 if pad_id is None else int(pad_id)
+
+    def end_of_step() -> bool:
+        """exchange, optimizer step, log, checkpoint; True when ``max_optimizer_steps`` is reached"""
+        nonlocal acc
+        tr.allreduce_grads(world)                           # the one exchange step of the path
+        tr.lr = lr_at(tr.step_count, cfg)
+        tr.step(world, max_grad_norm=cfg.max_grad_norm)
+        mean_loss = D.max_over_ranks(acc, 1)                # local value; rank 0 logs
+        losses.append(mean_loss)
+        if log:
+            log(dict(step=tr.step_count, loss=mean_loss, lr=tr.lr))
+        acc = 0.0
+        if output_dir and tr.step_count % save_steps == 0:
+            CK.save_checkpoint(tr, output_dir, save_total_limit, rank, hf_config, tokenizer)
+        return bool(max_optimizer_steps and tr.step_count >= max_optimizer_steps)
+
     for batch in batches:
+        if cfg.pack_sequences:
+            # the step's micro-batches, right padding stripped, as one stream of rows (data.plan_packed_step): one forward / backward
+            pending.append(batch)
+            micro += 1
+            if micro % accum:
+                continue
+            from .data import plan_packed_step
+
+            plan = plan_packed_step(pending, audio_cfg, pad_id)
+            plan.segments = [(b, st, fr.to(engine.device, torch.float32)) for (b, st, fr) in plan.segments]
+            loss = tr.forward_backward_packed(None, None, None, None, overlap_allreduce_world=world, last_micro_batch=cfg.max_grad_norm > 0, plan=plan)
+            acc, pending = float(loss.item()), []
+            if end_of_step():
+                break
+            continue
         ids = batch["input_ids"].to(engine.device)
         feats = batch.get("audio_encodings")
         if feats is not None:
@@ -125,19 +166,8 @@ def train(engine, batches: Iterable[Dict], audio_cfg, cfg: TrainConfig = TrainCo
         else:
             acc += run_micro(ids, segs, labels, last)
         micro += 1
-        if micro % accum == 0:
-            tr.allreduce_grads(world)                       # the one exchange step of the path
-            tr.lr = lr_at(tr.step_count, cfg)
-            tr.step(world, max_grad_norm=cfg.max_grad_norm)
-            mean_loss = D.max_over_ranks(acc, 1)            # local value; rank 0 logs
-            losses.append(mean_loss)
-            if log:
-                log(dict(step=tr.step_count, loss=mean_loss, lr=tr.lr))
-            acc = 0.0
-            if output_dir and tr.step_count % save_steps == 0:
-                CK.save_checkpoint(tr, output_dir, save_total_limit, rank, hf_config, tokenizer)
-            if max_optimizer_steps and tr.step_count >= max_optimizer_steps:
-                break
+        if micro % accum == 0 and end_of_step():
+            break
     if output_dir:
         CK.save_checkpoint(tr, output_dir, save_total_limit, rank, hf_config, tokenizer)
     return losses
@@ -171,21 +201,9 @@ def check_supported_recipe(args) -> None:
         raise NotImplementedError("--bf16 False: the HIP training step computes in the bf16 flow of the reference recipe")
 
 
-def main(argv=None):
-    """CLI with the flag names of ``m2t/train.py`` / ``scripts/training/train_llark.sh`` that the native loop implements:
-    python -m llark_amd.m2t.train --model_name_or_path <hf dir> --train_data_path 'shards-{000..127}.tar' --output_dir out \
-        --mm_hidden_size 4800 --mm_use_audio_start_end True --per_device_train_batch_size 2 --gradient_accumulation_steps 4 \
-        --learning_rate 5e-5 --warmup_ratio 0.03 --max_steps 100000 --model_max_length 2048 --save_steps 5000 --save_total_limit 1
-    (one process per GPU under ``python -m torch.distributed.run``)."""
+def build_arg_parser():
+    """The argument parser of :func:`main` (no model, tokenizer or GPU needed to build it)."""
     import argparse
-
-    import torch as _torch
-    from transformers import AutoTokenizer
-
-    from .. import dist as D
-    from .data import micro_batches
-    from .engine import HipLlamaEngine, LlamaDims
-    from .llamav2 import WrappedLlamav2ForCausalLM
 
     boolean = lambda v: str(v).lower() in ("1", "true", "yes")
     ap = argparse.ArgumentParser(description="LLark instruction tuning on the HIP training step")
@@ -209,6 +227,9 @@ def main(argv=None):
     ap.add_argument("--allow_pickle", type=boolean, default=False, help=".pyd shard members are pickles: enable only for trusted data")
     ap.add_argument("--fuse_accumulation", type=boolean, default=False,
                     help="not a reference flag: run the accumulation micro-batches of a step as one pass when they share a shape (same gradient; more HBM)")
+    ap.add_argument("--pack_sequences", type=boolean, default=False,
+                    help="not a reference flag: run the ragged micro-batches of a step as one packed stream (no pad rows, one pass over the weights; "
+                         "same loss and gradient; Llama only)")
     ap.add_argument("--gradient_checkpointing", type=boolean, default=False, help="train_llark.sh:25: recompute each decoder layer in the backward")
     ap.add_argument("--apply_task_sample_probs", type=boolean, default=False, help="m2t/arguments.py:68: weight shards by the task in their name")
     ap.add_argument("--task_sample_probs", default=None, help='JSON dict task -> probability (default: m2t/arguments.py:61-67)')
@@ -225,8 +246,24 @@ def main(argv=None):
     for ignored in ("--tf32", "--report_to", "--logging_steps", "--evaluation_strategy", "--save_strategy",
                     "--ddp_find_unused_parameters", "--dataloader_num_workers", "--num_train_epochs"):
         ap.add_argument(ignored, default=None, help="accepted for script compatibility (no effect on the arithmetic of the native loop)")
-    args = ap.parse_args(argv)
+    return ap
 
+
+def main(argv=None):
+    """CLI with the flag names of ``m2t/train.py`` / ``scripts/training/train_llark.sh`` that the native loop implements:
+    python -m llark_amd.m2t.train --model_name_or_path <hf dir> --train_data_path 'shards-{000..127}.tar' --output_dir out \
+        --mm_hidden_size 4800 --mm_use_audio_start_end True --per_device_train_batch_size 2 --gradient_accumulation_steps 4 \
+        --learning_rate 5e-5 --warmup_ratio 0.03 --max_steps 100000 --model_max_length 2048 --save_steps 5000 --save_total_limit 1
+    (one process per GPU under ``python -m torch.distributed.run``)."""
+    import torch as _torch
+    from transformers import AutoTokenizer
+
+    from .. import dist as D
+    from .data import micro_batches
+    from .engine import HipLlamaEngine, LlamaDims
+    from .llamav2 import WrappedLlamav2ForCausalLM
+
+    args = build_arg_parser().parse_args(argv)
     check_supported_recipe(args)
     rank, world, local = D.env_rank_world()
     _torch.cuda.set_device(local)
@@ -245,7 +282,8 @@ def main(argv=None):
     dims = LlamaDims(hidden_size=c.hidden_size, intermediate_size=c.intermediate_size, num_hidden_layers=c.num_hidden_layers,
                      num_attention_heads=c.num_attention_heads, vocab_size=len(tok), rms_norm_eps=c.rms_norm_eps,
                      rope_theta=getattr(c, "rope_theta", 10000.0), mm_hidden_size=args.mm_hidden_size)
-    eng = HipLlamaEngine(dims, dev, max_batch=args.per_device_train_batch_size * (args.gradient_accumulation_steps if args.fuse_accumulation else 1),
+    fused_step = args.fuse_accumulation or args.pack_sequences               # the engine then holds a whole step's rows at once
+    eng = HipLlamaEngine(dims, dev, max_batch=args.per_device_train_batch_size * (args.gradient_accumulation_steps if fused_step else 1),
                          max_seq=args.model_max_length, precision="bf16", frag_weights=False)
     eng.load_state_dict(model.state_dict())
     audio_cfg = model.get_model().audio_encoder_config
@@ -259,7 +297,7 @@ def main(argv=None):
     cfg = TrainConfig(learning_rate=args.learning_rate, weight_decay=args.weight_decay, warmup_ratio=args.warmup_ratio,
                       max_steps=args.max_steps, gradient_accumulation_steps=args.gradient_accumulation_steps, grad_comm=args.grad_comm,
                       gradient_checkpointing=args.gradient_checkpointing, max_grad_norm=args.max_grad_norm,
-                      fuse_accumulation=args.fuse_accumulation, freeze_backbone=args.freeze_backbone, lora_enable=args.lora_enable,
+                      fuse_accumulation=args.fuse_accumulation, pack_sequences=args.pack_sequences, freeze_backbone=args.freeze_backbone, lora_enable=args.lora_enable,
                       lora_r=args.lora_r, lora_alpha=args.lora_alpha, lora_dropout=args.lora_dropout, lora_bias=args.lora_bias,
                       seed=args.seed)
     task_probs = None

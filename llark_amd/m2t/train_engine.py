@@ -73,6 +73,19 @@ class _LoraGroup:
         self.a_cat = torch.zeros((self.k, w), **z)
 
 
+class _Packing:
+    """What a packed step (``forward_backward_packed``) changes in the body of ``forward_backward``: the rows are ONE stream (B = 1, S =
+    s_total) cut into sequences by ``seqs`` = [(off, len)] (device table ``table``); RoPE of a row uses its position inside its sequence
+    (``cos`` / ``sin``: the engine's tables gathered per row); the loss is normalised per group of rows (``groups`` = [(r0, r1)])."""
+
+    def __init__(self, plan, eng):
+        dev = eng.device
+        self.seqs, self.groups, self.max_len, self.s_total = list(plan.seqs), list(plan.groups), plan.max_len, plan.s_total
+        self.table = torch.tensor(self.seqs, dtype=torch.int32).to(dev)
+        pos = plan.positions.to(dev)
+        self.cos, self.sin = eng.cos.index_select(0, pos), eng.sin.index_select(0, pos)
+
+
 class HipLlamaTrainer:
     def __init__(self, engine: HipLlamaEngine, lr: float = 5e-5, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, embed_grad_tokens: Sequence[int] = (), train_embed_all: bool = False,
@@ -512,8 +525,36 @@ class HipLlamaTrainer:
         ops.gemm16(dy16, None, wT, None, w.shape[1], ops.EPI_F32, c=out)
 
     # ------------------------------------------------------------------------------------------
+    def forward_backward_packed(self, seqs, segs, labels, groups, loss_scale: Optional[float] = None, overlap_allreduce_world: int = 1,
+                                last_micro_batch: bool = False, pad_id: int = 0, plan=None) -> torch.Tensor:
+        """A whole optimizer step of ragged sequences as ONE packed stream: no padded sequence, one pass over the weights.
+        ``seqs`` / ``labels``: lists of 1-D id / label tensors of any lengths; ``segs``: (sequence index, start, frames) as in
+        :meth:`forward_backward`; ``groups``: the number of sequences in each micro-batch of the step.  The loss keeps the reference's
+        meaning -- each micro-batch's mean cross-entropy over ITS shifted targets, averaged over the micro-batches (``loss_scale``
+        defaults to 1 / len(groups)) -- so the gradient is the sum the separate right-padded micro-batches would accumulate.
+        Every sequence is padded to a multiple of 8 rows with ``pad_id`` / label -100 (data.pack_sequences; ``plan``: a PackedStep
+        built already, e.g. by data.plan_packed_step); attention runs on the variable-length kernels (llark_attn_*_varlen), RoPE uses
+        the position inside the sequence, and each layer's saved K / V^T live in that layer's own cache memory viewed as one sequence
+        of s_total positions."""
+        from .data import pack_sequences
+
+        if plan is None:
+            plan = pack_sequences(seqs, labels, groups, segs, pad_id)
+        eng = self.eng
+        if plan.s_total > eng.max_batch * eng.smax:
+            raise ValueError(f"forward_backward_packed: s_total = {plan.s_total} packed rows do not fit the engine's caches "
+                             f"(max_batch * smax = {eng.max_batch} * {eng.smax} positions)")
+        if plan.max_len > eng.cos.shape[0]:
+            raise ValueError(f"forward_backward_packed: a sequence of {plan.max_len} rows is beyond the RoPE table ({eng.cos.shape[0]} positions)")
+        if eng.dims.head_dim != 128:
+            raise ValueError("forward_backward_packed: the variable-length attention kernels need head_dim 128")
+        return self.forward_backward(plan.ids.view(1, -1).to(eng.device), plan.segments, plan.labels.view(1, -1),
+                                     1.0 / len(plan.groups) if loss_scale is None else loss_scale, overlap_allreduce_world, last_micro_batch,
+                                     _packing=_Packing(plan, eng))
+
     def forward_backward(self, input_ids: torch.Tensor, audio_segments, labels: torch.Tensor, loss_scale: float = 1.0,
-                         overlap_allreduce_world: int = 1, last_micro_batch: bool = False, loss_groups: int = 1) -> torch.Tensor:
+                         overlap_allreduce_world: int = 1, last_micro_batch: bool = False, loss_groups: int = 1,
+                         _packing: Optional[_Packing] = None) -> torch.Tensor:
         """One micro-batch: returns the (unscaled) loss as a device scalar and ACCUMULATES gradients.
         ``loss_scale`` = 1 / gradient_accumulation_steps like HF Trainer.
         ``loss_groups`` > 1: the batch holds that many of the recipe's micro-batches (consecutive, equal-sized groups of sequences) run
@@ -550,7 +591,17 @@ class HipLlamaTrainer:
         H, I, nh, hd, V = d.hidden_size, d.intermediate_size, d.num_attention_heads, d.head_dim, d.vocab_size
         f32 = dict(dtype=torch.float32, device=dev)
         bf = dict(dtype=_BF, device=dev)
-        eng.reset(B)
+        pk = _packing                                                   # a packed step (forward_backward_packed): B = 1, S = s_total
+        eng.reset(B if pk is None else eng.max_batch)
+        if pk is None:
+            smax = eng.smax
+            caches = lambda i: (eng.k_cache[i, :B], eng.vt_cache[i, :B])            # [B][nh][smax][hd], [B][nh][hd][smax]
+            cos, sin = eng.cos, eng.sin
+        else:
+            # the caches are scratch during training: a layer's saved K / V^T are ONE sequence of S positions at the head of its own memory
+            smax = S
+            caches = lambda i: (eng.k_cache[i].view(-1)[: nh * S * hd].view(1, nh, S, hd), eng.vt_cache[i].view(-1)[: nh * S * hd].view(1, nh, hd, S))
+            cos, sin = pk.cos, pk.sin                                   # row r rotates by its position inside its sequence
         ids_flat = input_ids.reshape(-1).contiguous()
         h = torch.empty((rows, H), **f32)
         ops.embed_gather(ids_flat, eng.embed, h)
@@ -558,7 +609,7 @@ class HipLlamaTrainer:
         for (b, start, frames) in audio_segments:
             F = frames.shape[0]
             a16, _ = ops.split16(frames.contiguous(), _BF, want_lo=False, kmult=64)
-            r0 = b * S + start + 1
+            r0 = (b * S if pk is None else pk.seqs[b][0]) + start + 1
             ops.gemm16(a16, None, eng.proj_w, eng.proj_b, H, ops.EPI_F32, c=h[r0: r0 + F])
             seg_rows.append(torch.arange(r0, r0 + F, device=dev))
             seg_a16.append(a16[:, : d.mm_hidden_size])
@@ -575,24 +626,27 @@ class HipLlamaTrainer:
             # augmented K: x1 = [RMSNorm(h) | T] with T = x A^T in the tail columns, against the [W | sB] twin
             x1, x1w = self._norm_aug(h, L.ln1, lg.get((i, "qkv")) if fused_qkv and self.lora_aug else None, st, "t_qkv")
             q = torch.empty((B, nh, S, hd), **bf)
-            kc, vc = eng.k_cache[i, :B], eng.vt_cache[i, :B]
+            kc, vc = caches(i)
             v_rm = None
             if fused_qkv:                                                # RoPE / head split / K and V^T writes in the product's epilogue
                 if self.attn_glue_fused:                                 # ... and V row-major for the backward (no transpose16 of the V^T cache)
                     v_rm = torch.empty((B * nh, S, hd), **bf)
-                    ops.gemm16_fragw_rope_qkv_train(x1w, tw[0], x1w.shape[1], B, S, nh, 0, eng.cos, eng.sin, q, kc, vc, v_rm)
+                    ops.gemm16_fragw_rope_qkv_train(x1w, tw[0], x1w.shape[1], B, S, nh, 0, cos, sin, q, kc, vc, v_rm)
                 else:
-                    ops.gemm16_fragw_rope_qkv(x1w, None, tw[0], x1w.shape[1], B, S, nh, 0, eng.cos, eng.sin, q, kc, vc)
+                    ops.gemm16_fragw_rope_qkv(x1w, None, tw[0], x1w.shape[1], B, S, nh, 0, cos, sin, q, kc, vc)
             else:
                 qkv = torch.empty((rows, 3 * H), **f32)
                 ops.gemm16(x1, None, self._fwd_weight(L.wqkv), None, 3 * H, ops.EPI_F32, c=qkv)
                 if (i, "qkv") in lg:
                     st["t_qkv"] = self._lora_fwd(lg[(i, "qkv")], x1, qkv)
-                ops.rope_split_heads(qkv, B, S, nh, hd, 0, eng.cos, eng.sin, q, kc, vc)
+                ops.rope_split_heads(qkv, B, S, nh, hd, 0, cos, sin, q, kc, vc)
                 del qkv
             att = torch.empty((rows, H), **bf)
             lse = torch.empty((B * nh, S), **f32)                         # per-query log-sum-exp: the backward recomputes P from it
-            ops.attn_prefill_lse(q, kc, vc, B, S, nh, hd, att, lse)
+            if pk is None:
+                ops.attn_prefill_lse(q, kc, vc, B, S, nh, hd, att, lse)
+            else:
+                ops.attn_prefill_lse_varlen(q, kc, vc, pk.table, pk.seqs, pk.max_len, S, nh, hd, att, lse)
             h_mid = torch.empty_like(h)
             ops.gemm16(att, None, self._fwd_weight(L.wo), None, H, ops.EPI_RESID, c=h_mid, resid=h)
             if (i, "o") in lg:
@@ -637,7 +691,15 @@ class HipLlamaTrainer:
         ops.gemm16(xf, None, eng.lm_head, None, V, ops.EPI_F32, c=logits)
         Vp = ops.round_up(V, 64)
         dlogits = torch.empty((rows, Vp), **bf)
-        if loss_groups > 1:
+        if pk is not None:
+            # per micro-batch: the mean over ITS shifted targets.  Every sequence's first label is -100, so no row predicts across a
+            # boundary; a group's last row is the last position of its (1, rows) call and does not count either.
+            lab, loss = labels.reshape(-1).to(dev), None
+            for (r0, r1) in pk.groups:
+                li = ops.cross_entropy_fwd_bwd(logits[r0:r1].view(1, r1 - r0, V), lab[r0:r1].view(1, r1 - r0), dlogits[r0:r1], loss_scale)
+                loss = li if loss is None else loss + li
+            loss = loss / len(pk.groups)
+        elif loss_groups > 1:
             assert B % loss_groups == 0, "loss_groups must divide the batch"
             gb, lab = B // loss_groups, labels.to(dev)
             lg = logits.view(B, S, V)
@@ -666,7 +728,6 @@ class HipLlamaTrainer:
         Sp = ops.round_up(S, 64)
         BH = B * nh
         scale = 1.0 / math.sqrt(hd)
-        smax = eng.smax
         for i in reversed(range(len(eng.layers))):
             L, st = eng.layers[i], saved[i]
             if self.gradient_checkpointing:          # recompute this layer's forward from its saved input (K / V caches included)
@@ -712,8 +773,7 @@ class HipLlamaTrainer:
                 dh16, _ = ops.split16(dh, _BF, want_lo=False, kmult=64)
                 dh16 = dh16[:, :H]
             q = st["q"].view(BH, S, hd)
-            kc = eng.k_cache[i, :B]                                      # [B][nh][smax][hd]
-            vtc = eng.vt_cache[i, :B]                                    # [B][nh][hd][smax]
+            kc, vtc = caches(i)
             # flash-style backward (csrc/attn_bwd.hip): P is recomputed per tile from the forward's log-sum-exp, no S x S matrix
             # exists and no operand is transposed
             v_rm = st.get("v_rm")
@@ -739,7 +799,11 @@ class HipLlamaTrainer:
                     ops.gemm16_fragw(dh16w, None, tw[1], None, H, H, ops.EPI_OUT16, out_hi=datt16)
                 if not frozen:
                     self._dw(dh16, st["att"], g[pre + "wo"], pre + "wo")
-                ops.attn_backward_fused(q, kc, v_rm, datt16, st["att"], st["lse"], dsum, B, S, nh, hd, eng.cos, eng.sin, 0, dqkv)
+                if pk is None:
+                    ops.attn_backward_fused(q, kc, v_rm, datt16, st["att"], st["lse"], dsum, B, S, nh, hd, eng.cos, eng.sin, 0, dqkv)
+                else:                                                       # (the engine's own tables: the kernel rotates by the position inside the sequence)
+                    ops.attn_backward_fused_varlen(q, kc, v_rm, datt16, st["att"], st["lse"], dsum, pk.table, pk.seqs, pk.max_len, S, nh, hd,
+                                                   eng.cos, eng.sin, dqkv)
             else:
                 self._dx(dh16, L.wo, dtmp)                                  # d(att)
                 if (i, "o") in lg:
@@ -752,8 +816,11 @@ class HipLlamaTrainer:
                 dq = torch.empty((BH, S, hd), **f32)
                 dk = torch.empty((BH, S, hd), **f32)
                 dv = torch.empty((BH, S, hd), **f32)
-                ops.attn_backward(q, kc, v_rm, dO, st["att"], st["lse"], dsum, B, S, nh, hd, dq, dk, dv)
-                ops.rope_merge_bwd(dq, dk, dv, eng.cos, eng.sin, B, S, nh, hd, 0, dqkv)
+                if pk is None:
+                    ops.attn_backward(q, kc, v_rm, dO, st["att"], st["lse"], dsum, B, S, nh, hd, dq, dk, dv)
+                else:
+                    ops.attn_backward_varlen(q, kc, v_rm, dO, st["att"], st["lse"], dsum, pk.table, pk.seqs, pk.max_len, S, nh, hd, dq, dk, dv)
+                ops.rope_merge_bwd(dq, dk, dv, cos, sin, B, S, nh, hd, 0, dqkv)
             self._dx(dqkv, L.wqkv, dtmp)
             if (i, "qkv") in lg:
                 self._lora_bwd(lg[(i, "qkv")], dqkv, st["x1"], st["t_qkv"], dtmp)

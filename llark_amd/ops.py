@@ -1458,6 +1458,77 @@ def attn_backward_fused(q, k_cache, v_rm, dO: torch.Tensor, o, lse, dsum, batch:
         _dev(sin_t, "sin", f32), pos0, cos_t.shape[0], _dev(dqkv, "dqkv", bf), _stream()), "attn_backward_fused")
 
 
+# ---- variable-length (packed) attention of the training step (include/llark_hip.h: llark_attn_*_varlen) ---------------------------------------
+def check_seq_table(seqs_host, max_len: int, s_total: int, name: str = "seqs") -> None:
+    """The table contract of the variable-length attention entry points, checked on the host list of ``(off, len)`` the device table was
+    built from; raises ``ValueError`` naming the rule that is broken."""
+    if len(seqs_host) == 0:
+        raise ValueError(f"{name}: the table is empty")
+    end = 0
+    for b, (off, ln) in sorted(enumerate(seqs_host), key=lambda e: e[1][0]):
+        off, ln = int(off), int(ln)
+        if off < 0 or off % 8 != 0:
+            raise ValueError(f"{name}[{b}]: off % 8 == 0 is required (the forward reads V^T in chunks of 8 keys), got off = {off}")
+        if ln < 1:
+            raise ValueError(f"{name}[{b}]: len >= 1 is required, got {ln}")
+        if off + ln > s_total:
+            raise ValueError(f"{name}[{b}]: off + len <= s_total is required, got {off} + {ln} > {s_total}")
+        if ln > max_len:
+            raise ValueError(f"{name}[{b}]: max_len >= max(len) is required, got len = {ln} > max_len = {max_len}")
+        if off < end:
+            raise ValueError(f"{name}[{b}]: ranges must be disjoint, rows {off}..{off + ln - 1} overlap the range that ends at row {end - 1}")
+        end = off + ln
+
+
+def _seq_table(seqs: torch.Tensor, seqs_host, max_len: int, s_total: int) -> int:
+    check_seq_table(seqs_host, max_len, s_total)
+    if seqs.dtype != torch.int32 or tuple(seqs.shape) != (len(seqs_host), 2):
+        raise ValueError(f"seqs: expected an int32 device tensor [{len(seqs_host)}][2], got {seqs.dtype} {tuple(seqs.shape)}")
+    return _dev(seqs, "seqs", torch.int32)
+
+
+def attn_prefill_lse_varlen(q, k_cache, vt_cache, seqs: torch.Tensor, seqs_host, max_len: int, s_total: int, nh: int, hd: int,
+                            out: torch.Tensor, lse: torch.Tensor) -> None:
+    """:func:`attn_prefill_lse` over the sequences of a table: the layouts of a ``batch = 1, s = s_total`` call, ``seqs`` int32 [nseq][2] =
+    (off, len) on the device, ``seqs_host`` the host list it was built from (checked here: :func:`check_seq_table`)."""
+    table = _seq_table(seqs, seqs_host, max_len, s_total)
+    smax = k_cache.shape[-2]
+    bf = torch.bfloat16
+    with _timed("attn_prefill_lse_varlen", 0.0):
+        check(_lib.lib().llark_attn_prefill_bf16_lse_varlen(_dev(q, "q", bf), _dev(k_cache, "k_cache", bf), _dev(vt_cache, "vt_cache", bf), table,
+                                                            len(seqs_host), max_len, s_total, nh, hd, smax, _dev(out, "out", bf),
+                                                            _dev(lse, "lse", torch.float32), _stream()), "attn_prefill_lse_varlen")
+
+
+def attn_backward_varlen(q, k_cache, v_rm, dO, o, lse, dsum, seqs: torch.Tensor, seqs_host, max_len: int, s_total: int, nh: int, hd: int,
+                         dq: torch.Tensor, dk: torch.Tensor, dv: torch.Tensor) -> None:
+    """:func:`attn_backward` over the sequences of a table (see :func:`attn_prefill_lse_varlen`)."""
+    table = _seq_table(seqs, seqs_host, max_len, s_total)
+    smax = k_cache.shape[-2]
+    bf, f32 = torch.bfloat16, torch.float32
+    with _timed("attn_backward_varlen", 0.0):
+        check(_lib.lib().llark_attn_backward_bf16_varlen(_dev(q, "q", bf), _dev(k_cache, "k_cache", bf), _dev(v_rm, "v_rm", bf), _dev(dO, "dO", bf),
+                                                         _dev(o, "o", bf), _dev(lse, "lse", f32), _dev(dsum, "dsum", f32), table, len(seqs_host),
+                                                         max_len, s_total, nh, hd, smax, _dev(dq, "dq", f32), _dev(dk, "dk", f32),
+                                                         _dev(dv, "dv", f32), _stream()), "attn_backward_varlen")
+
+
+def attn_backward_fused_varlen(q, k_cache, v_rm, dO: torch.Tensor, o, lse, dsum, seqs: torch.Tensor, seqs_host, max_len: int, s_total: int,
+                               nh: int, hd: int, cos_t: torch.Tensor, sin_t: torch.Tensor, dqkv: torch.Tensor) -> None:
+    """:func:`attn_backward_fused` over the sequences of a table; the RoPE backward of row ``off + i`` uses ``cos_t[i]``, the position inside
+    the sequence (``cos_t`` / ``sin_t`` are the engine's own tables, ``max_len <= cos_t.shape[0]``)."""
+    table = _seq_table(seqs, seqs_host, max_len, s_total)
+    smax = k_cache.shape[-2]
+    bf, f32 = torch.bfloat16, torch.float32
+    assert dO.dtype == bf and dO.stride(1) == 1 and dO.shape[0] >= s_total and dO.shape[1] >= nh * hd
+    assert dqkv.dtype == bf and dqkv.is_contiguous() and dqkv.shape == (s_total, 3 * nh * hd)
+    with _timed("attn_backward_fused_varlen", 0.0):
+        check(_lib.lib().llark_attn_backward_bf16_fused_varlen(
+            _dev(q, "q", bf), _dev(k_cache, "k_cache", bf), _dev(v_rm, "v_rm", bf), _dev(dO, "dO", bf, contiguous=False), dO.stride(0),
+            _dev(o, "o", bf), _dev(lse, "lse", f32), _dev(dsum, "dsum", f32), table, len(seqs_host), max_len, s_total, nh, hd, smax,
+            _dev(cos_t, "cos", f32), _dev(sin_t, "sin", f32), cos_t.shape[0], _dev(dqkv, "dqkv", bf), _stream()), "attn_backward_fused_varlen")
+
+
 # ---- decode-step launches chained across their boundaries (include/llark_hip.h: llark_gemv16_dma_chain) -----------------------------------
 def gemv16_dma_blocks(epilogue: int, n: int) -> int:
     """Grid size of a streaming-Linear launch: what its arrival counter advances by per launch."""
