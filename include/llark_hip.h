@@ -400,6 +400,23 @@ int llark_gemv16_dma_rmsnorm(int split, int epilogue, const float* x, int ldx, c
                              const float* bias, int m, int n, int kp, float* c, int ldc, void* out_hi, void* out_lo, int ldo,
                              llark_stream_t stream);
 
+/* Decode-step Linear for 17 <= m <= 64 activation rows (the ragged decode step with more than 16 slots; csrc/gemm_mid.hip):
+ * c[m][n] = sum_k (a_hi [+ a_lo])[m][k] wt[n][k] (+ bias[n]), bf16 operands, fp32 accumulate; wt is the row-major [n][ldw] tensor
+ * llark_gemm16 reads.  Every weight byte is read from HBM once per launch; a workgroup owns 128 (bf16 flow) or 256 (split flow) output
+ * columns and shares its activation chunk through LDS; K is cut over workgroups so that a 256-CU chip is filled, fp32 partial sums
+ * meet in `scratch` and a second launch adds them in a fixed order -- no atomics, nothing waits.  Output row r is bit-identical
+ * whatever m is, whatever the other rows hold and from launch to launch.
+ * epilogue: LLARK_EPI_F32, LLARK_EPI_RESID (resid may alias c), LLARK_EPI_SWIGLU16 / LLARK_EPI_SWIGLU_SPLIT (wt rows interleaved
+ * [gate 32 | up 32], n % 64 == 0, out [m][n / 2]).  kp % 32 == 0; lda, ldw >= kp and % 8 == 0; a_hi / a_lo / wt / scratch 16-byte
+ * aligned; ldc, ldr, ldo free.  Rows >= m and columns >= n are never stored.  dtype: LLARK_BF16 (LLARK_F16 and m outside 17 .. 64
+ * return LLARK_ERR_UNSUPPORTED); every rule is checked before any launch and llark_last_error names the argument.
+ * scratch: caller-owned, at least llark_gemm16_mid_scratch_bytes(...) bytes = splits x m x (n rounded up to the column tile) x 4, where
+ * splits (1 .. 8) depends on n, kp and split only; 0 = the shape or epilogue is refused. */
+long long llark_gemm16_mid_scratch_bytes(int m, int n, int kp, int split, int epilogue);
+int llark_gemm16_mid(int dtype, int split, int epilogue, const void* a_hi, const void* a_lo, int lda, const void* wt, int ldw,
+                     const float* bias, int m, int n, int kp, float* c, int ldc, const float* resid, int ldr, void* out_hi, void* out_lo,
+                     int ldo, void* scratch, long long scratch_bytes, llark_stream_t stream);
+
 /* Backward products of nn.Linear without transposed copies of their operands (csrc/gemm_tn.hip; torch autograd of the Linear
  * layers under WrappedLlamav2ForCausalLM.forward + loss.backward(), m2t/models/llamav2.py:259-337, m2t/train.py:53-277):
  *   c[m][n] (= | +=) sum_k A(m, k) W(n, k), 16-bit operands, fp32 accumulate / output.

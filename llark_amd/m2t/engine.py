@@ -382,7 +382,16 @@ class HipLlamaEngine:
             return
         if not normed:
             ops.rmsnorm_bf16(h, self.norm, d.rms_norm_eps, ws["x16"], ws["x16_lo"])
+        if self._mid_step(ws, h.shape[0]):
+            ops.gemm16_mid(ws["x16"], ws["x16_lo"], self.lm_head, None, d.vocab_size, ops.EPI_F32, ws["mid"], c=logits)
+            return
         ops.gemm16(ws["x16"], ws["x16_lo"], self.lm_head, None, d.vocab_size, ops.EPI_F32, c=logits)
+
+    @staticmethod
+    def _mid_step(ws, batch: int) -> bool:
+        """Is this the ragged decode step with 17 .. 64 slots?  Its workspace (_slot_workspace) then carries the scratch of the mid-M
+        weight-streaming GEMM (ops.gemm16_mid); every other workspace has none and keeps the launches it always had."""
+        return ws.get("mid") is not None and 16 < batch <= 64
 
     def _head_rows(self, hl: torch.Tensor) -> torch.Tensor:
         """Final norm + lm_head on gathered rows hl fp32 [n][H] -> fp32 logits [n][V]."""
@@ -414,7 +423,8 @@ class HipLlamaEngine:
         """The decoder layers of a decode step.  Decided once, here: `fused` (o_proj / down_proj carry the FOLLOWING RMSNorm in their
         launch), `norm_a` (RMSNorm inside the consuming weight-streaming GEMM) and the attention form -- "rows" (ragged: each slot at its
         own position), "rope" (RoPE + cache append inside the attention launch), "dpos" (position in device memory, graph-capturable)
-        or "plain" (rope_split_heads + attn_decode)."""
+        or "plain" (rope_split_heads + attn_decode).  The ragged step with 17 .. 64 slots (`mid`) runs the unfused sequence on
+        ops.gemm16_mid, the weight-streaming GEMM for that row count; every other case keeps ops.gemm16."""
         d = self.dims
         H, I, nh, hd, eps, sp = d.hidden_size, d.intermediate_size, d.num_attention_heads, d.head_dim, d.rms_norm_eps, self.split
         fused = batch <= 16 and n_layers > 0 and self.fuse_decode_norm and H <= 8192 and hidden_sink is None
@@ -427,6 +437,7 @@ class HipLlamaEngine:
             return False
         attn = "rows" if pos_rows is not None else "rope" if self.fuse_decode_rope else "dpos" if pos_dev is not None else "plain"
         pos = pos_rows if attn == "rows" else pos_dev if pos_dev is not None else pos0
+        mid = ws["mid"] if pos_rows is not None and self._mid_step(ws, batch) else None      # 17 .. 64 slots: rmsnorm_bf16 + gemm16_mid
         epi_gu, cos, sin = self._epi_swiglu(), self.cos, self.sin
         h, qkv, x16, x16l, q, ql = ws["h"], ws["qkv"], ws["x16"], ws["x16_lo"], ws["q"], ws["q_lo"]
         att, attl, act, actl = ws["att"], ws["att_lo"], ws["act"], ws["act_lo"]
@@ -440,7 +451,10 @@ class HipLlamaEngine:
             else:
                 if not fused:
                     ops.rmsnorm_bf16(h, L.ln1, eps, x16, x16l)
-                ops.gemm16(x16, x16l, L.wqkv, None, 3 * H, ops.EPI_F32, c=qkv)
+                if mid is not None:
+                    ops.gemm16_mid(x16, x16l, L.wqkv, None, 3 * H, ops.EPI_F32, mid, c=qkv)
+                else:
+                    ops.gemm16(x16, x16l, L.wqkv, None, 3 * H, ops.EPI_F32, c=qkv)
             if attn == "rows":
                 ops.attn_decode_rope_rows(qkv, batch, nh, hd, pos, cos, sin, kc, vc, att, kcl, vcl, attl)
             elif attn == "rope":
@@ -456,6 +470,12 @@ class HipLlamaEngine:
                 ops.gemm16(x16, x16l, L.wgu, None, 2 * I, epi_gu, out_hi=act, out_lo=actl)
                 nxt = self.layers[i + 1].ln1 if i + 1 < n_layers else self.norm
                 ops.gemm16_resid_rmsnorm(act, actl, L.wdown, h, nxt, eps, x16, x16l)
+                continue
+            if mid is not None:
+                ops.gemm16_mid(att, attl, L.wo, None, H, ops.EPI_RESID, mid, c=h, resid=h)
+                ops.rmsnorm_bf16(h, L.ln2, eps, x16, x16l)
+                ops.gemm16_mid(x16, x16l, L.wgu, None, 2 * I, epi_gu, mid, out_hi=act, out_lo=actl)
+                ops.gemm16_mid(act, actl, L.wdown, None, H, ops.EPI_RESID, mid, c=h, resid=h)
                 continue
             ops.gemm16(att, attl, L.wo, None, H, ops.EPI_RESID, c=h, resid=h)
             if norm_a:
@@ -677,8 +697,13 @@ class HipLlamaEngine:
     # ---- ragged mode: batch slots with their own cache lengths ---------------------------------------------------------
     # Next to the uniform forward_tokens / cur_len mode (which it leaves untouched): slot b of the KV cache holds one sequence of
     # slot_len[b] tokens (-1 = idle).  prefill_slots fills slots with new prompts at position 0 while the other slots keep their
-    # state, decode_slots runs one token for every slot at its own position, release_slots frees slots for a refill.  The decode
-    # GEMMs are the m <= 16 forms, hence at most 16 slots.
+    # state, decode_slots runs one token for every slot at its own position, release_slots frees slots for a refill.  Up to 16
+    # slots the decode GEMMs are the m <= 16 forms (skinny / streaming kernels, RMSNorm fused where they take it); 17 .. 64 slots run
+    # rmsnorm_bf16 + ops.gemm16_mid (csrc/gemm_mid.hip: the same weights streamed once, activations shared through LDS, K split over
+    # workgroups with its partial sums in the slot workspace).  Both are row-independent: a slot's logits do not depend on its
+    # neighbours or on the slot count within one of the two ranges.  64 rows is what gemm16_mid takes, hence at most 64 slots.
+    MAX_SLOTS = 64
+
     def _clear_slots(self) -> None:
         self.n_slots = 0
         self.slot_len = self.slot_state = None                 # device int32 [n_slots]: positions, ops.ROW_* states
@@ -687,9 +712,16 @@ class HipLlamaEngine:
 
     def init_slots(self, n_slots: int) -> None:
         """Enter the ragged mode with `n_slots` idle slots (the KV cache is (re)sized to n_slots sequences)."""
-        if not 1 <= n_slots <= min(self.max_batch, 16):
-            raise ValueError(f"n_slots must be in 1 .. {min(self.max_batch, 16)} (max_batch {self.max_batch}, decode GEMMs m <= 16), got {n_slots}")
-        self.reset(n_slots)
+        top = min(self.max_batch, self.MAX_SLOTS)
+        if not 1 <= n_slots <= top:
+            raise ValueError(f"n_slots must be in 1 .. {top} (max_batch {self.max_batch}, decode GEMMs m <= {self.MAX_SLOTS}), got {n_slots}")
+        try:
+            self.reset(n_slots)
+        except torch.cuda.OutOfMemoryError as e:
+            d = self.dims
+            per_slot = d.num_hidden_layers * d.hidden_size * self.smax * 2 * 2 * (2 if self.split else 1)
+            raise RuntimeError(f"init_slots({n_slots}): the KV cache does not fit: {per_slot / 2**30:.2f} GiB per slot x {n_slots} slots "
+                               f"(max_seq {self.smax}, precision {self.precision!r}); use fewer slots or a smaller max_seq") from e
         self.n_slots = n_slots
         self.slot_len = torch.full((n_slots,), -1, dtype=torch.int32, device=self.device)
         self.slot_state = torch.full((n_slots,), ops.ROW_IDLE, dtype=torch.int32, device=self.device)
@@ -767,6 +799,16 @@ class HipLlamaEngine:
             ws = self._alloc_workspace(n, 1)
             ws["logits"] = torch.empty((n, self.dims.vocab_size), dtype=torch.float32, device=self.device)
             ws["next"] = torch.zeros((n,), dtype=torch.int64, device=self.device)
+            if 16 < n <= self.MAX_SLOTS:                       # scratch of ops.gemm16_mid: the largest of the step's five products
+                d = self.dims
+                H, I = d.hidden_size, d.intermediate_size
+                need = [ops.gemm16_mid_scratch_bytes(n, nn, w.shape[1], self.split, epi) for nn, w, epi in (
+                    (3 * H, self.layers[0].wqkv, ops.EPI_F32), (H, self.layers[0].wo, ops.EPI_RESID),
+                    (2 * I, self.layers[0].wgu, self._epi_swiglu()), (H, self.layers[0].wdown, ops.EPI_RESID),
+                    (d.vocab_size, self.lm_head, ops.EPI_F32))]
+                if min(need) == 0:
+                    raise ops._lib.LlarkHipError(f"gemm16_mid does not take this model's decode shapes (H {H}, I {I}, {n} slots)")
+                ws["mid"] = torch.empty((max(need) // 4,), dtype=torch.float32, device=self.device)
             self._slot_ws = ws
         return self._slot_ws
 
@@ -790,8 +832,8 @@ class HipLlamaEngine:
 
     def decode_slots(self, ids: torch.Tensor, eos: int = -1, pad: int = 0, out_col: Optional[torch.Tensor] = None,
                      sample=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """One decode step over all n_slots rows, each at its own position: embedding -> decoder layers (the uniform decode GEMMs;
-        attention by ops.attn_decode_rope_rows over slot_len) -> final norm + lm_head -> advance_slots.  ids: int64 [n_slots] (the
+        """One decode step over all n_slots rows, each at its own position: embedding -> decoder layers (the uniform decode GEMMs up
+        to 16 slots, ops.gemm16_mid for 17 .. 64; attention by ops.attn_decode_rope_rows over slot_len) -> final norm + lm_head -> advance_slots.  ids: int64 [n_slots] (the
         token of each slot at position slot_len; idle rows pass through the row-independent GEMMs harmlessly).  sample: optional
         callable logits -> int64 [n_slots] tokens (sampling); greedy otherwise.  Returns (next ids on the device, their host copy,
         the step's fp32 logits [n_slots, V] -- a buffer the next step overwrites)."""

@@ -451,7 +451,8 @@ def main_shards(argv=None):
     ap.add_argument("--outfile", default="infer_results.csv")
     ap.add_argument("--max-samples", type=int, default=None)
     ap.add_argument("--max_new_tokens", type=int, default=2048)
-    ap.add_argument("--slots", type=int, default=8)
+    ap.add_argument("--slots", type=int, default=8, help="examples that decode together, 1 .. 64 (each slot holds a KV cache of "
+                    "--model_max_length positions: about 1 GiB per slot at 7B, 1024 positions, split precision)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--allow-pickle", action="store_true")
     ap.add_argument("--mm_hidden_size", type=int, default=None)
@@ -460,6 +461,8 @@ def main_shards(argv=None):
     for ignored in ("--ckpt-num", "--report_to", "--bf16", "--tf32", "--output_dir"):
         ap.add_argument(ignored, default=None, help="accepted for script compatibility")
     args = ap.parse_args(argv)
+    if not 1 <= args.slots <= 64:
+        ap.error(f"--slots must be in 1 .. 64, got {args.slots}")
     model, tok, end_seq, mm_cfg = _load_for_inference(args, args.slots)
     recs = infer_from_shards(model, tok, args.eval_data_path, mm_cfg, end_seq, outfile=args.outfile, slots=args.slots,
                              max_samples=args.max_samples, max_new_tokens=args.max_new_tokens, prompt=args.prompt, seed=args.seed,

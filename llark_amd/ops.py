@@ -745,6 +745,33 @@ def gemm16_rmsnorm_a(x: torch.Tensor, norm_w: torch.Tensor, eps: float, wt: torc
             "gemm16_rmsnorm_a")
 
 
+def gemm16_mid_scratch_bytes(m: int, n: int, kp: int, split: bool, epilogue: int) -> int:
+    """Bytes of scratch :func:`gemm16_mid` needs for the shape; 0 = the shape or epilogue is refused (include/llark_hip.h)."""
+    return int(_lib.lib().llark_gemm16_mid_scratch_bytes(int(m), int(n), int(kp), int(split), int(epilogue)))
+
+
+def gemm16_mid(a_hi: torch.Tensor, a_lo: Optional[torch.Tensor], wt: torch.Tensor, bias: Optional[torch.Tensor], n: int, epilogue: int,
+               scratch: torch.Tensor, c: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
+               out_hi: Optional[torch.Tensor] = None, out_lo: Optional[torch.Tensor] = None, m: Optional[int] = None) -> None:
+    """Decode step with 17 .. 64 rows: C[m,n] = (a_hi [+ a_lo]) . wt^T (+bias), epilogue EPI_F32 / EPI_RESID / SwiGLU, bf16
+    (csrc/gemm_mid.hip).  ``scratch``: a caller-owned device buffer of at least :func:`gemm16_mid_scratch_bytes` bytes."""
+    bf = torch.bfloat16
+    m = a_hi.shape[0] if m is None else m
+    kp = wt.shape[1]
+    assert a_hi.shape[1] >= kp and wt.shape[0] >= n, f"gemm16_mid: A has {a_hi.shape[1]} cols, wt {tuple(wt.shape)}, n={n}"
+    name = ("gemm_split_" if a_lo is not None else "gemm_") + "bf16_mid"
+    for t in (a_hi, a_lo, wt, c, resid, out_hi, out_lo):                  # row strides are free (lda / ldw / ldc / ldr / ldo), columns are not
+        assert t is None or t.stride(-1) == 1, "gemm16_mid: rows must be contiguous"
+    assert out_lo is None or out_lo.stride(0) == out_hi.stride(0) and (a_lo is None or a_lo.stride(0) == a_hi.stride(0))
+    nc = dict(contiguous=False)
+    with _timed(name, 2.0 * m * n * kp):
+        check(_lib.lib().llark_gemm16_mid(
+            _DT[bf], int(a_lo is not None), epilogue, _dev(a_hi, "a_hi", bf, **nc), _opt(a_lo, "a_lo", bf, **nc), a_hi.stride(0),
+            _dev(wt, "wt", bf, **nc), wt.stride(0), _opt(bias, "bias", torch.float32), m, n, kp, _opt(c, "c", torch.float32, **nc), _ld(c),
+            _opt(resid, "resid", torch.float32, **nc), _ld(resid), _opt(out_hi, "out_hi", bf, **nc), _opt(out_lo, "out_lo", bf, **nc),
+            _ld(out_hi), _dev(scratch, "scratch"), scratch.numel() * scratch.element_size(), _stream()), "gemm16_mid")
+
+
 def pack_weight16_frag(wt: torch.Tensor, n: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """wt [>=n][kp] 16-bit (pack_weight16 output, kp % 64 == 0) -> fragment-major copy for gemm16_fragw
     (``out``: an existing copy of the same shape to re-pack in place)."""
@@ -948,12 +975,13 @@ def attn_decode_rope_rows(qkv: torch.Tensor, batch: int, nh: int, hd: int, pos_r
     for c in (k_cache_lo, vt_cache_lo):
         assert c is None or c.shape in (k_cache.shape, vt_cache.shape)
     assert alibi_slopes is None or alibi_slopes.numel() >= nh
-    check(_lib.lib().llark_attn_decode_rope_bf16_rows(_dev(qkv, "qkv", torch.float32), batch, nh, hd, _dev(pos_rows, "pos_rows", torch.int32),
-                                                      _dev(cos_t, "cos", torch.float32), _dev(sin_t, "sin", torch.float32), cos_t.shape[0],
-                                                      _dev(k_cache, "k_cache", bf), _dev(vt_cache, "vt_cache", bf),
-                                                      _opt(k_cache_lo, "k_cache_lo", bf), _opt(vt_cache_lo, "vt_cache_lo", bf), smax,
-                                                      _dev(out, "out", bf), _opt(out_lo, "out_lo", bf),
-                                                      _opt(alibi_slopes, "alibi_slopes", torch.float32), _stream()), "attn_decode_rope_rows")
+    with _timed("attn_decode_rope_rows", 0.0):
+        check(_lib.lib().llark_attn_decode_rope_bf16_rows(_dev(qkv, "qkv", torch.float32), batch, nh, hd, _dev(pos_rows, "pos_rows", torch.int32),
+                                                          _dev(cos_t, "cos", torch.float32), _dev(sin_t, "sin", torch.float32), cos_t.shape[0],
+                                                          _dev(k_cache, "k_cache", bf), _dev(vt_cache, "vt_cache", bf),
+                                                          _opt(k_cache_lo, "k_cache_lo", bf), _opt(vt_cache_lo, "vt_cache_lo", bf), smax,
+                                                          _dev(out, "out", bf), _opt(out_lo, "out_lo", bf),
+                                                          _opt(alibi_slopes, "alibi_slopes", torch.float32), _stream()), "attn_decode_rope_rows")
 
 
 def decode_advance_rows(logits: Optional[torch.Tensor], state: torch.Tensor, next_ids: torch.Tensor, pos_rows: Optional[torch.Tensor] = None,

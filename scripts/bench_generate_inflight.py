@@ -7,10 +7,14 @@ clip of 121 frames), prompt texts of 8-80 tokens, seeded per-example answer budg
   (a) batch1   -- model.generate per example;
   (b) grouped  -- generate_batch over groups of up to 8 examples sharing one prompt length (what the uniform engine allows), each
                   group decoding until its longest budget, rows cut at their own budget;
-  (c) inflight -- generate_inflight with 8 and with 16 slots.
-Also the decode-step time of the ragged step with every slot active (1, 8, 16 slots).  Prints ONE JSON line.
+  (c) inflight -- generate_inflight with every slot count of --slots (default 8, 16, 32, 64; above 16 slots the decode step runs on
+                  ops.gemm16_mid).
+Also the decode-step time of the ragged step with every slot active (1, 8, 16, 32, 48, 64 slots) and, at 16 and 64 slots, the
+per-kernel split of one step from ops kernel timing.  Prints ONE JSON line.
 
-    python scripts/bench_generate_inflight.py [--examples 64] [--precision split] [--seed 0]
+    python scripts/bench_generate_inflight.py [--slots 8,16,32,64] [--examples N] [--schedules batch1,grouped,inflight]
+                                              [--precision split] [--seed 0]
+--examples defaults to 256 when a slot count above 16 is asked for (64 slots stay full for most of the run), 64 otherwise.
 """
 import argparse
 import json
@@ -135,45 +139,74 @@ def decode_step_ms(model, examples, n_slots, steps=32):
     for _ in range(steps):
         ids, _, _ = eng.decode_slots(ids)
     torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / steps * 1e3
+    ms = (time.perf_counter() - t0) / steps * 1e3
+    split = None
+    if n_slots in (16, 64):                                   # where one step's time goes: device time per kernel tag, one step
+        from llark_amd import ops
+        ops.start_kernel_timing()
+        ids, _, _ = eng.decode_slots(ids)
+        split = {k: round(v[1], 3) for k, v in sorted(ops.stop_kernel_timing().items(), key=lambda kv: -kv[1][1])}
+    return ms, split
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--examples", type=int, default=64)
+    ap.add_argument("--slots", default="8,16,32,64", help="slot counts of the inflight schedule, 1 .. 64 each")
+    ap.add_argument("--examples", type=int, default=None, help="default: 256 with a slot count above 16, else 64")
+    ap.add_argument("--schedules", default="batch1,grouped,inflight", help="which schedules to time")
     ap.add_argument("--precision", default="split", choices=["split", "bf16"])
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_generate_inflight needs the GPU")
-    examples = make_examples(args.examples, args.seed)
+    slot_list = [int(x) for x in args.slots.split(",") if x]
+    if not slot_list or any(not 1 <= n <= 64 for n in slot_list):
+        ap.error(f"--slots takes counts in 1 .. 64, got {args.slots!r}")
+    schedules = set(args.schedules.split(","))
+    n_examples = args.examples if args.examples is not None else (256 if max(slot_list) > 16 else 64)
+    step_slots = [n for n in (1, 8, 16, 32, 48, 64) if n <= max(16, max(slot_list))]
+    examples = make_examples(n_examples, args.seed)
     max_seq = max(ids.numel() + b for ids, _, b in examples) + 8
-    model = RandomLlama(args.precision, 16, max_seq)
+    model = RandomLlama(args.precision, max(step_slots), max_seq)
     tok = _NoText()
     gen_tokens = sum(b for _, _, b in examples)
     warm = [(ids, enc, 4) for ids, enc, _ in examples[:16]]
     run_batch1(model, warm[:2], tok)
     run_grouped(model, warm, tok)
-    run_inflight(model, warm, 8)
-    run_inflight(model, warm, 16)
+    for slots in slot_list:
+        run_inflight(model, (warm * 4)[: max(16, slots)], slots)
     res = {"bench": "generate_inflight", "model": "llama2-7b dims, random weights", "precision": args.precision,
            "examples": len(examples), "frames": {"240": sum(e[1].shape[0] == 240 for e in examples),
                                                   "121": sum(e[1].shape[0] == 121 for e in examples)},
            "prompt_tokens": [min(e[0].numel() for e in examples), max(e[0].numel() for e in examples)],
            "generated_tokens": gen_tokens, "schedules": {}}
-    outs_a, t = timed(lambda: run_batch1(model, examples, tok))
-    res["schedules"]["batch1"] = {"s": round(t, 3), "clips_per_s": round(len(examples) / t, 3), "tokens_per_s": round(gen_tokens / t, 1)}
-    (outs_b, groups), t = timed(lambda: run_grouped(model, examples, tok))
-    res["schedules"]["grouped_b8"] = {"s": round(t, 3), "clips_per_s": round(len(examples) / t, 3), "tokens_per_s": round(gen_tokens / t, 1),
-                                      "generate_calls": groups, "mean_rows_per_call": round(len(examples) / groups, 2)}
-    for slots in (8, 16):
+    outs_a = None
+    if "batch1" in schedules:
+        outs_a, t = timed(lambda: run_batch1(model, examples, tok))
+        res["schedules"]["batch1"] = {"s": round(t, 3), "clips_per_s": round(len(examples) / t, 3), "tokens_per_s": round(gen_tokens / t, 1)}
+    if "grouped" in schedules:
+        (outs_b, groups), t = timed(lambda: run_grouped(model, examples, tok))
+        res["schedules"]["grouped_b8"] = {"s": round(t, 3), "clips_per_s": round(len(examples) / t, 3), "tokens_per_s": round(gen_tokens / t, 1),
+                                          "generate_calls": groups, "mean_rows_per_call": round(len(examples) / groups, 2)}
+    first = None                                              # without batch1: the first slot count's outputs are what the others are compared to
+    for slots in slot_list if "inflight" in schedules else ():
         (outs_c, prefills), t = timed(lambda: run_inflight(model, examples, slots))
-        same = sum(torch.equal(outs_c[i].cpu(), outs_a[i].cpu()) for i in range(len(examples)))
         assert all(outs_c[i].numel() == examples[i][0].numel() + examples[i][2] for i in range(len(examples)))
-        res["schedules"][f"inflight_{slots}"] = {"s": round(t, 3), "clips_per_s": round(len(examples) / t, 3),
-                                                 "tokens_per_s": round(gen_tokens / t, 1), "prefill_calls": prefills,
-                                                 "outputs_equal_to_batch1": same}
-    res["decode_step_ms"] = {str(n): round(decode_step_ms(model, examples, n), 3) for n in (1, 8, 16)}
+        row = {"s": round(t, 3), "clips_per_s": round(len(examples) / t, 3), "tokens_per_s": round(gen_tokens / t, 1), "prefill_calls": prefills}
+        if outs_a is not None:
+            row["outputs_equal_to_batch1"] = sum(torch.equal(outs_c[i].cpu(), outs_a[i].cpu()) for i in range(len(examples)))
+        elif first is not None:
+            row[f"outputs_equal_to_inflight_{slot_list[0]}"] = sum(torch.equal(outs_c[i].cpu(), first[i]) for i in range(len(examples)))
+        else:
+            first = {i: o.cpu() for i, o in outs_c.items()}
+        res["schedules"][f"inflight_{slots}"] = row
+    res["decode_step_ms"], res["decode_step_kernels_ms"] = {}, {}
+    for n in step_slots:
+        ms, split = decode_step_ms(model, examples, n)
+        res["decode_step_ms"][str(n)] = round(ms, 3)
+        res["decode_step_ms_per_slot"] = {k: round(v / int(k), 4) for k, v in res["decode_step_ms"].items()}
+        if split is not None:
+            res["decode_step_kernels_ms"][str(n)] = split
     print(json.dumps(res), flush=True)
 
 
