@@ -544,6 +544,37 @@ int llark_attn_decode_rope_bf16_rows(const float* qkv, int batch, int nh, int hd
                                      int smax, void* out, void* out_lo, const float* alibi_slopes, llark_stream_t stream);
 int llark_decode_advance_rows(const float* logits, int ldl, int vocab, int batch, const int64_t* choice, int* pos_rows, int* state,
                               int64_t* next_ids, int64_t* out_col, int ld_out, int64_t eos, int64_t pad, llark_stream_t stream);
+/* Shared prompt prefix in the ragged slot mode (csrc/attn_shared.hip).  Under the contract of infer_from_webdataset.py every
+ * (question, answer) pair of a sample is its own example and all of them start with the same audio block: the slots of one clip hold
+ * the same K/V at their first positions.
+ *   llark_kv_copy_prefix (engine.fork_slots: a sibling's slot receives the prefix instead of prefilling it): positions [0, n) of cache
+ *     slot `src` into each of the n_dst slots of `dst` (a HOST array), all layers, the lo planes too when given (both or none).  Whole
+ *     caches: k [layers][slots][nh][smax][128], v^T [layers][slots][nh][128][smax].  V^T rows move in 16-byte chunks, so positions
+ *     n .. round_up(n, 8) - 1 of a destination are overwritten too (dead until the decode step appends there, like pad positions);
+ *     nothing at or beyond round_up(n, 8) is written.  LLARK_ERR_UNSUPPORTED: n outside 1 .. smax, src among dst, a slot twice in dst,
+ *     more than 64 destinations, hd != 128, smax % 8 != 0.
+ *   llark_attn_decode_rope_bf16_shared (engine.decode_slots with share_prefix): llark_attn_decode_rope_bf16_rows -- same arguments,
+ *     same caches, same outputs, no ALiBi -- plus a group table in DEVICE memory:
+ *       groups int32 [n_groups][19] = {source slot, P, members m (1 .. 16), member slot 0 .. m - 1, unused};
+ *       slot_shared int32 [batch]: P of the slot's group, 0 = in no group.
+ *     Keys [0, P) of a member are read from the source slot's cache, once for the whole group (they must be bit-identical to the
+ *     member's own; P % 8 == 0, P <= the position of every member and of the source); keys [P, pos] from the member's own cache.  A
+ *     slot with slot_shared == 0 gets exactly the bits of llark_attn_decode_rope_bf16_rows, output and caches.  Two launches in stream
+ *     order (group pass, per-slot pass + merge); no workgroup waits for another.  scratch: caller-owned, 16-byte aligned, at least
+ *     llark_attn_decode_shared_scratch_bytes(batch, nh) bytes = 64 + batch * nh * 4 key ranges * 132 floats, zeroed once by the caller;
+ *     its first int32 is a status word: the table lives on the device, so the KERNEL refuses a bad one -- it stores a nonzero code
+ *     there (1: P not a positive multiple of 8 or > smax, 2: members outside 1 .. 16, 3: P greater than a member's position, or that
+ *     member idle or at smax, 4: source slot inactive or shorter than P, 5: member slot out of range or slot_shared[member] != P),
+ *     the group pass of that group computes nothing and the outputs of its members are undefined.  The word is sticky: the caller
+ *     reads and clears it (ops.attn_decode_shared_status).  LLARK_ERR_UNSUPPORTED from the host: hd != 128, n_groups > batch,
+ *     smax > 32768. */
+int llark_kv_copy_prefix(void* k_cache, void* vt_cache, void* k_cache_lo, void* vt_cache_lo, int layers, int slots, int nh, int hd,
+                         int smax, int src, const int* dst, int n_dst, int n, llark_stream_t stream);
+long long llark_attn_decode_shared_scratch_bytes(int batch, int nh);
+int llark_attn_decode_rope_bf16_shared(const float* qkv, int batch, int nh, int hd, const int* pos_rows, const float* cos_t,
+                                       const float* sin_t, int max_pos, void* k_cache, void* vt_cache, void* k_cache_lo,
+                                       void* vt_cache_lo, int smax, void* out, void* out_lo, const int* groups, int n_groups,
+                                       const int* slot_shared, void* scratch, long long scratch_bytes, llark_stream_t stream);
 /* Decode-step forms with the sequence position in DEVICE memory (*pos_dev = tokens already cached = position of the
  * new token; s = 1): lets ONE captured hipGraph of the whole decode step serve every generated token of
  * m2t/models/llamav2.py:339-365 / m2t/infer.py:137-148. */

@@ -436,7 +436,9 @@ class HipLlamaEngine:
             self._decode_layers_chained(ws, pos0, n_layers)
             return False
         attn = "rows" if pos_rows is not None else "rope" if self.fuse_decode_rope else "dpos" if pos_dev is not None else "plain"
-        pos = pos_rows if attn == "rows" else pos_dev if pos_dev is not None else pos0
+        if attn == "rows" and self._groups is not None and pos_rows is self.slot_len and ws.get("attn_shared") is not None:
+            attn = "shared"                                   # share_prefix with at least one group: the slots of a clip read their prefix once
+        pos = pos_rows if attn in ("rows", "shared") else pos_dev if pos_dev is not None else pos0
         mid = ws["mid"] if pos_rows is not None and self._mid_step(ws, batch) else None      # 17 .. 64 slots: rmsnorm_bf16 + gemm16_mid
         epi_gu, cos, sin = self._epi_swiglu(), self.cos, self.sin
         h, qkv, x16, x16l, q, ql = ws["h"], ws["qkv"], ws["x16"], ws["x16_lo"], ws["q"], ws["q_lo"]
@@ -457,6 +459,9 @@ class HipLlamaEngine:
                     ops.gemm16(x16, x16l, L.wqkv, None, 3 * H, ops.EPI_F32, c=qkv)
             if attn == "rows":
                 ops.attn_decode_rope_rows(qkv, batch, nh, hd, pos, cos, sin, kc, vc, att, kcl, vcl, attl)
+            elif attn == "shared":
+                ops.attn_decode_rope_shared(qkv, batch, nh, hd, pos, cos, sin, kc, vc, att, self._groups, self._slot_shared, ws["attn_shared"],
+                                            kcl, vcl, attl)
             elif attn == "rope":
                 ops.attn_decode_rope(qkv, batch, nh, hd, pos, cos, sin, kc, vc, att, kcl, vcl, attl)
             elif attn == "dpos":
@@ -709,9 +714,20 @@ class HipLlamaEngine:
         self.slot_len = self.slot_state = None                 # device int32 [n_slots]: positions, ops.ROW_* states
         self.slot_len_host: List[int] = []
         self.slot_state_host: List[int] = []
+        # shared prefixes (fork_slots): lineage id of a slot (None: none), its leading positions bit-identical to the lineage's root,
+        # forked slots that still wait for their suffix (slot -> n), and the group table of the decode step (share_prefix only)
+        self.share_prefix = False
+        self.slot_lineage: List[Optional[int]] = []
+        self.slot_shared_host: List[int] = []
+        self._forked: Dict[int, int] = {}
+        self._lineages = 0
+        self.group_list: List[Tuple[int, int, List[int]]] = []       # (source slot, shared length, member slots) as uploaded
+        self._groups = self._slot_shared = None                      # device int32 [n_groups][ops.SHARED_GROUP_STRIDE], [n_slots]
 
-    def init_slots(self, n_slots: int) -> None:
-        """Enter the ragged mode with `n_slots` idle slots (the KV cache is (re)sized to n_slots sequences)."""
+    def init_slots(self, n_slots: int, share_prefix: bool = False) -> None:
+        """Enter the ragged mode with `n_slots` idle slots (the KV cache is (re)sized to n_slots sequences).  share_prefix: the decode
+        step reads the positions that the active slots of one lineage (fork_slots) have in common once per group
+        (ops.attn_decode_rope_shared) instead of once per slot; off, every launch is the one it always was."""
         top = min(self.max_batch, self.MAX_SLOTS)
         if not 1 <= n_slots <= top:
             raise ValueError(f"n_slots must be in 1 .. {top} (max_batch {self.max_batch}, decode GEMMs m <= {self.MAX_SLOTS}), got {n_slots}")
@@ -726,6 +742,10 @@ class HipLlamaEngine:
         self.slot_len = torch.full((n_slots,), -1, dtype=torch.int32, device=self.device)
         self.slot_state = torch.full((n_slots,), ops.ROW_IDLE, dtype=torch.int32, device=self.device)
         self.slot_len_host, self.slot_state_host = [-1] * n_slots, [ops.ROW_IDLE] * n_slots
+        self.share_prefix = bool(share_prefix)
+        self.slot_lineage, self.slot_shared_host = [None] * n_slots, [0] * n_slots
+        if self.share_prefix:
+            self._slot_shared = torch.zeros((n_slots,), dtype=torch.int32, device=self.device)
 
     def _check_slots(self, slots: Sequence[int]) -> List[int]:
         if self.n_slots == 0:
@@ -747,15 +767,89 @@ class HipLlamaEngine:
         slots = self._check_slots(slots)
         if slots:
             self._set_slots(slots, [-1] * len(slots), ops.ROW_IDLE)
+            self._drop_lineage(slots)
+
+    # ---- shared prefixes ---------------------------------------------------------------------------------------------------
+    # The examples of one clip start with the same tokens (conversation header + audio block).  fork_slots copies the K/V of those
+    # positions from a slot that holds them into idle slots (ops.kv_copy_prefix: no prefill of the prefix), prefill_slots(past=...)
+    # runs only the suffix through the layers, and with share_prefix the decode step reads the common positions once per group.
+    # Untuned default: below this many common positions a group is not worth its extra launch and merge (no measurement moved it yet).
+    MIN_SHARED = 64
+
+    def _drop_lineage(self, slots: Sequence[int]) -> None:
+        """Slots that were released or refilled from position 0 leave their lineage."""
+        hit = False
+        for b in slots:
+            hit = hit or self.slot_lineage[b] is not None or b in self._forked
+            self.slot_lineage[b], self.slot_shared_host[b] = None, 0
+            self._forked.pop(b, None)
+        if hit:
+            self._rebuild_groups()
+
+    def fork_slots(self, src: int, dsts: Sequence[int], n: int) -> None:
+        """Copy positions [0, n) of the active slot `src` into the idle slots `dsts` (every layer and plane, one launch) and leave
+        each of them "forked, awaiting suffix": slot_len = n on the host, still idle for the decode step until
+        prefill_slots(..., past=[n]) has run its suffix.  src and dsts become one lineage (a new one if src had none); a slot's shared
+        length is the number of its leading positions that are bit-identical to the lineage's root."""
+        src, dsts = self._check_slots([src])[0], self._check_slots(dsts)
+        if self.slot_state_host[src] != ops.ROW_ACTIVE or src in self._forked:
+            raise ValueError(f"fork_slots: source slot {src} is not active")
+        busy = [b for b in dsts if self.slot_len_host[b] >= 0 or b in self._forked]
+        if busy or src in dsts:
+            raise ValueError(f"fork_slots: destination slots {busy or [src]} are not idle")
+        if not 1 <= n <= self.slot_len_host[src]:
+            raise ValueError(f"fork_slots: n={n} outside 1 .. {self.slot_len_host[src]} (the source's length)")
+        if not dsts:
+            return
+        ops.kv_copy_prefix(self.k_cache, self.vt_cache, src, dsts, n, self.k_cache_lo, self.vt_cache_lo)
+        if self.slot_lineage[src] is None:                      # src is the root: everything it holds is the root's
+            self.slot_lineage[src], self.slot_shared_host[src] = self._lineages, self.smax
+            self._lineages += 1
+        for b in dsts:
+            self.slot_lineage[b], self.slot_shared_host[b] = self.slot_lineage[src], min(n, self.slot_shared_host[src])
+            self._forked[b], self.slot_len_host[b] = n, n
+
+    def _rebuild_groups(self) -> None:
+        """The decode step's group table, from the host's view of the slots: the non-idle slots of one lineage (forked ones only once
+        their suffix is in) form a group; its shared length is the smallest of its members', rounded down to a multiple of 8 (the
+        per-slot V^T pass starts on a 16-byte chunk); its source is its lowest slot, so a released leader is simply no longer used.
+        More than 16 members are cut into several groups; fewer than 2, or fewer than MIN_SHARED positions: no group."""
+        if not self.share_prefix:
+            return
+        by_lineage: Dict[int, List[int]] = {}
+        for b in range(self.n_slots):
+            if self.slot_lineage[b] is not None and self.slot_len_host[b] >= 0 and b not in self._forked:
+                by_lineage.setdefault(self.slot_lineage[b], []).append(b)
+        groups: List[Tuple[int, int, List[int]]] = []
+        for members in by_lineage.values():
+            for c0 in range(0, len(members), ops.SHARED_GROUP_MEMBERS):
+                chunk = members[c0:c0 + ops.SHARED_GROUP_MEMBERS]
+                P = min(min(self.slot_shared_host[b], self.slot_len_host[b]) for b in chunk) // 8 * 8
+                if len(chunk) >= 2 and P >= self.MIN_SHARED:
+                    groups.append((chunk[0], P, chunk))
+        if groups == self.group_list:
+            return
+        self.group_list = groups
+        shared = [0] * self.n_slots
+        tab = torch.zeros((max(1, len(groups)), ops.SHARED_GROUP_STRIDE), dtype=torch.int32)
+        for g, (src, P, chunk) in enumerate(groups):
+            tab[g, :3 + len(chunk)] = torch.tensor([src, P, len(chunk)] + chunk, dtype=torch.int32)
+            for b in chunk:
+                shared[b] = P
+        self._groups = tab.to(self.device) if groups else None
+        self._slot_shared.copy_(torch.tensor(shared, dtype=torch.int32))
 
     def prefill_slots(self, rows: Sequence[torch.Tensor], audio_segments: Sequence[Tuple[int, int, torch.Tensor]] = (),
-                      slots: Optional[Sequence[int]] = None) -> torch.Tensor:
+                      slots: Optional[Sequence[int]] = None, past: Optional[Sequence[int]] = None) -> torch.Tensor:
         """Prefill new sequences into the given slots at position 0; the other slots keep their caches and positions.
         rows: 1-D int64 token tensors (one per new sequence); audio_segments: (index into rows, position of <audio_start>, frames
         fp32 (F, mm)) as in forward_tokens; slots: the slot of each row (default 0 .. len(rows) - 1).  A run of contiguous slots is
         prefilled as ONE right-padded batch: causal attention never lets a valid position see a pad, and the cache rows written for
         pad positions lie beyond the slot's length, where the decode step overwrites them before it reads them.
-        Returns fp32 logits [len(rows), V] of each row's LAST valid token; sets slot_len = row length, state active."""
+        Returns fp32 logits [len(rows), V] of each row's LAST valid token; sets slot_len = row length, state active.
+        past: one start position per row.  A row with past > 0 holds only the SUFFIX tokens of a slot that fork_slots left at exactly
+        that length: they run through the layers at positions past .. (the prefill-with-past path of forward_tokens) on top of the
+        copied prefix; such a row must carry no audio segment.  Runs are then cut by contiguity and equal past."""
         d = self.dims
         assert self.embed is not None and all(L is not None for L in self.layers), "weights not loaded"
         slots = self._check_slots(range(len(rows)) if slots is None else slots)
@@ -763,6 +857,8 @@ class HipLlamaEngine:
             raise ValueError(f"{len(rows)} rows for {len(slots)} slots")
         rows = [r.reshape(-1).to(device=self.device, dtype=torch.int64) for r in rows]
         lens = [int(r.numel()) for r in rows]
+        if past is not None:
+            return self._prefill_slots_past(rows, lens, audio_segments, slots, [int(p) for p in past])
         if any(n < 1 or n > self.smax for n in lens):
             raise ValueError(f"row lengths {lens} must be in 1 .. max_seq {self.smax}")
         logits = torch.empty((len(rows), d.vocab_size), dtype=torch.float32, device=self.device)
@@ -782,14 +878,55 @@ class HipLlamaEngine:
             last = torch.tensor([i * S + lens[r] - 1 for i, r in enumerate(run)], dtype=torch.long, device=self.device)
             logits[torch.tensor(run, dtype=torch.long, device=self.device)] = self._prefill_run(ids, segs, slots[run[0]], last)
         self._set_slots(slots, lens, ops.ROW_ACTIVE)
+        self._drop_lineage(slots)
         return logits
 
-    def _prefill_run(self, ids: torch.Tensor, segs, slot0: int, last: torch.Tensor) -> torch.Tensor:
-        """forward_tokens(last_only=True) of a right-padded batch into cache slots slot0 .., logits of the rows of h listed in `last`."""
+    def _prefill_slots_past(self, rows, lens: List[int], audio_segments, slots: List[int], past: List[int]) -> torch.Tensor:
+        """prefill_slots with start positions: rows with past == 0 as ever, the others as suffixes of forked slots."""
+        if len(past) != len(rows):
+            raise ValueError(f"{len(past)} start positions for {len(rows)} rows")
+        for r, (b, p, n) in enumerate(zip(slots, past, lens)):
+            if p < 0 or n < 1 or p + n > self.smax:
+                raise ValueError(f"row {r}: positions {p} .. {p + n - 1} outside 0 .. max_seq {self.smax} - 1")
+            if p > 0 and self._forked.get(b) != p:
+                raise ValueError(f"row {r}: slot {b} was not forked to length {p} (fork_slots first)")
+            if p > 0 and any(rr == r for (rr, _, _) in audio_segments):
+                raise ValueError(f"row {r}: a suffix (past {p}) must contain no audio tokens")
+            if p == 0 and b in self._forked:
+                raise ValueError(f"row {r}: slot {b} awaits the suffix of its fork at {self._forked[b]}")
+        logits = torch.empty((len(rows), self.dims.vocab_size), dtype=torch.float32, device=self.device)
+        order = sorted(range(len(rows)), key=lambda r: slots[r])
+        runs: List[List[int]] = []
+        for r in order:
+            if runs and slots[r] == slots[runs[-1][-1]] + 1 and past[r] == past[runs[-1][-1]]:
+                runs[-1].append(r)
+            else:
+                runs.append([r])
+        for run in runs:
+            nb, S = len(run), max(lens[r] for r in run)
+            ids = torch.zeros((nb, S), dtype=torch.int64, device=self.device)
+            for i, r in enumerate(run):
+                ids[i, : lens[r]] = rows[r]
+            segs = [(i, start, frames) for i, r in enumerate(run) for (rr, start, frames) in audio_segments if rr == r]
+            last = torch.tensor([i * S + lens[r] - 1 for i, r in enumerate(run)], dtype=torch.long, device=self.device)
+            logits[torch.tensor(run, dtype=torch.long, device=self.device)] = self._prefill_run(ids, segs, slots[run[0]], last, past[run[0]])
+        self._set_slots(slots, [p + n for p, n in zip(past, lens)], ops.ROW_ACTIVE)
+        fresh = [b for b, p in zip(slots, past) if p == 0]
+        for b, p in zip(slots, past):
+            if p > 0:
+                del self._forked[b]
+        if fresh:
+            self._drop_lineage(fresh)
+        self._rebuild_groups()
+        return logits
+
+    def _prefill_run(self, ids: torch.Tensor, segs, slot0: int, last: torch.Tensor, pos0: int = 0) -> torch.Tensor:
+        """forward_tokens(last_only=True) of a right-padded batch into cache slots slot0 .. at positions pos0 .., logits of the rows of
+        h listed in `last`."""
         B, S = ids.shape
         ws = self._workspace(B, S)
         embed_splice(ids, self.embed, ws["h"], segs, self.proj_w, self.proj_b, self.split)
-        self._layers_forward(ws, B, S, 0, slot0=slot0)
+        self._layers_forward(ws, B, S, pos0, slot0=slot0)
         return self._head_rows(ws["h"].index_select(0, last))
 
     def _slot_workspace(self):
@@ -810,6 +947,9 @@ class HipLlamaEngine:
                     raise ops._lib.LlarkHipError(f"gemm16_mid does not take this model's decode shapes (H {H}, I {I}, {n} slots)")
                 ws["mid"] = torch.empty((max(need) // 4,), dtype=torch.float32, device=self.device)
             self._slot_ws = ws
+        if self.share_prefix and "attn_shared" not in self._slot_ws:   # partials of ops.attn_decode_rope_shared; word 0 = its status, zero
+            need = ops.attn_decode_shared_scratch_bytes(n, self.dims.num_attention_heads)
+            self._slot_ws["attn_shared"] = torch.zeros((need // 4,), dtype=torch.float32, device=self.device)
         return self._slot_ws
 
     def advance_slots(self, logits: torch.Tensor, eos: int = -1, pad: int = 0, out_col: Optional[torch.Tensor] = None,

@@ -84,6 +84,9 @@ def generate_batch(model, input_ids: torch.Tensor, encodings: torch.Tensor, toke
     return [out[b, : (done_at[b] if done_at[b] is not None else out.shape[1])] for b in range(B)]
 
 
+MIN_SHARED = 64      # fewest common leading tokens worth a fork; the engine's own (untuned) default, HipLlamaEngine.MIN_SHARED
+
+
 class InflightScheduler:
     """Slot table of :func:`generate_inflight`, free of any GPU code so that it can run against a fake backend.
 
@@ -94,18 +97,29 @@ class InflightScheduler:
       * ``release(slots)``: the slots' examples are done.
     Free slots are refilled in ascending slot order with examples in input order; a row stops on a keyword (``stop_fn``), on
     ``eos`` or at its budget, exactly as :func:`generate_batch` decides per row.  ``trace`` records ``("prefill", slots, indices)``
-    and ``("done", slot, index)`` events."""
+    and ``("done", slot, index)`` events.
 
-    def __init__(self, backend, n_slots: int, max_new_tokens: int = 512, eos: Optional[int] = None, stop_fn=None):
+    ``share_prefix``: an example may carry a ``prefix_key`` (equal keys promise equal audio encodings: the questions of one clip).
+    When one is admitted while a slot of the same key is active -- or is being prefilled in the same round -- and the two prompts
+    have at least ``min_shared`` leading tokens in common (capped at the new prompt's length - 1, the rest free of the backend's
+    ``audio_token_ids``), the backend copies those positions (``fork(src, dsts, n)``) and prefills only the rest
+    (``prefill(slots, suffixes, [None, ...], past=[n, ...])``); the trace gains ``("fork", src, dst, n)``.  The examples that need a full
+    prefill go first, in one call as ever; a backend without ``fork`` gets nothing but full prefills.  Off (the default), calls and
+    trace are exactly what they were."""
+
+    def __init__(self, backend, n_slots: int, max_new_tokens: int = 512, eos: Optional[int] = None, stop_fn=None,
+                 share_prefix: bool = False, min_shared: int = MIN_SHARED):
         if n_slots < 1:
             raise ValueError(f"n_slots must be >= 1, got {n_slots}")
         self.backend, self.n_slots, self.max_new_tokens = backend, n_slots, max_new_tokens
+        self.share_prefix = bool(share_prefix) and hasattr(backend, "fork")
+        self.min_shared = min_shared
         self.eos = eos if eos is not None and eos >= 0 else None
         self.stop_fn = stop_fn                    # (prompt ids, generated ids) -> bool: keyword stop; may keep state per row
         self.trace: List[Tuple] = []
 
     def run(self, examples: Iterable[Sequence[Any]]) -> Iterator[Tuple[int, torch.Tensor]]:
-        """examples: (prompt_ids, encoding[, max_new_tokens]).  Yields (input index, prompt + generated ids) as rows finish; rows
+        """examples: (prompt_ids, encoding[, max_new_tokens[, prefix_key]]).  Yields (input index, prompt + generated ids) as rows finish; rows
         finishing in the same step come out in input order."""
         it = enumerate(examples)
         exhausted = False
@@ -122,12 +136,11 @@ class InflightScheduler:
                 prompt = torch.as_tensor(ex[0], dtype=torch.int64).reshape(-1).cpu()
                 budget = int(ex[2]) if len(ex) > 2 and ex[2] is not None else self.max_new_tokens
                 b = free.pop(0)
-                table[b] = {"index": idx, "prompt": prompt, "enc": ex[1], "budget": budget, "out": [], "stop": None}
+                table[b] = {"index": idx, "prompt": prompt, "enc": ex[1], "budget": budget, "out": [], "stop": None,
+                            "key": ex[3] if len(ex) > 3 else None}
                 new.append(b)
             if new:
-                self.trace.append(("prefill", tuple(new), tuple(table[b]["index"] for b in new)))
-                firsts = self.backend.prefill(new, [table[b]["prompt"] for b in new], [table[b]["enc"] for b in new])
-                done = self._take(table, dict(zip(new, firsts)))
+                done = self._take(table, self._admit(table, new))
                 yield from done
                 if done and not exhausted:
                     continue                       # refill the slots that finished at once before the next decode step
@@ -137,6 +150,53 @@ class InflightScheduler:
                 continue
             toks = self.backend.decode()
             yield from self._take(table, {b: toks[b] for b in range(self.n_slots) if table[b] is not None})
+
+    def _admit(self, table, new: List[int]) -> Dict[int, int]:
+        """Prefill the examples just placed in the slots ``new``; returns slot -> first token."""
+        forks = self._plan_forks(table, new) if self.share_prefix else {}
+        full = [b for b in new if b not in forks]
+        toks: Dict[int, int] = {}
+        if full:
+            self.trace.append(("prefill", tuple(full), tuple(table[b]["index"] for b in full)))
+            toks.update(zip(full, self.backend.prefill(full, [table[b]["prompt"] for b in full], [table[b]["enc"] for b in full])))
+        if forks:
+            calls: Dict[Tuple[int, int], List[int]] = {}
+            for b in sorted(forks):
+                calls.setdefault(forks[b], []).append(b)
+            for (src, n), dsts in calls.items():
+                for b in dsts:
+                    self.trace.append(("fork", src, b, n))
+                self.backend.fork(src, dsts, n)
+            forked = sorted(forks)
+            self.trace.append(("prefill", tuple(forked), tuple(table[b]["index"] for b in forked)))
+            firsts = self.backend.prefill(forked, [table[b]["prompt"][forks[b][1]:] for b in forked], [None] * len(forked),
+                                          past=[forks[b][1] for b in forked])
+            toks.update(zip(forked, firsts))
+        return toks
+
+    def _plan_forks(self, table, new: List[int]) -> Dict[int, Tuple[int, int]]:
+        """slot -> (source slot, n) for the new examples that start like a slot of their key which is active, or which gets its
+        full prefill in this round (the first of several new siblings).  The longest common prefix wins, then the lowest slot."""
+        audio = set(getattr(self.backend, "audio_token_ids", ()))
+        forks: Dict[int, Tuple[int, int]] = {}
+        sources = [b for b in range(self.n_slots) if table[b] is not None and b not in new]
+        for b in new:
+            row = table[b]
+            best = None
+            for src in sources if row["key"] is not None else ():
+                if table[src]["key"] != row["key"]:
+                    continue
+                a, p = table[src]["prompt"], row["prompt"]
+                m = min(a.numel(), p.numel())
+                diff = (a[:m] != p[:m]).nonzero()
+                n = min(int(diff[0]) if diff.numel() else m, p.numel() - 1)
+                if n >= self.min_shared and not any(int(t) in audio for t in p[n:]) and (best is None or n > best[1]):
+                    best = (src, n)
+            if best is not None:
+                forks[b] = best
+            else:
+                sources.append(b)                     # prefilled in full first: later siblings of this round fork from it
+        return forks
 
     def _take(self, table, toks: Dict[int, int]) -> List[Tuple[int, torch.Tensor]]:
         finished = []
@@ -163,16 +223,25 @@ class EngineSlots:
     """:class:`InflightScheduler` backend on the HIP engine's ragged slot mode (``HipLlamaEngine.init_slots`` /
     ``prefill_slots`` / ``decode_slots`` / ``release_slots``) of a ``WrappedLlamav2ForCausalLM``."""
 
-    def __init__(self, model, n_slots: int):
+    def __init__(self, model, n_slots: int, share_prefix: bool = False):
         from .llamav2 import plan_audio_splice
 
         self._plan = plan_audio_splice
         self.model = model
         self.eng = model.engine
-        self.eng.init_slots(n_slots)
+        if share_prefix:
+            self.eng.init_slots(n_slots, share_prefix=True)
+        else:
+            self.eng.init_slots(n_slots)
         self.ids = torch.zeros((n_slots,), dtype=torch.int64, device=self.eng.device)
+        cfg = model.get_model().audio_encoder_config
+        self.audio_token_ids = tuple(int(t) for t in (getattr(cfg, name, None) for name in ("audio_start_token", "audio_end_token", "audio_patch_token"))
+                                     if t is not None)
 
-    def prefill(self, slots, prompts, encodings):
+    def fork(self, src, dsts, n):
+        self.eng.fork_slots(src, dsts, n)
+
+    def prefill(self, slots, prompts, encodings, past=None):
         eng = self.eng
         cfg = self.model.get_model().audio_encoder_config
         segs = []
@@ -180,7 +249,10 @@ class EngineSlots:
             if enc is not None:
                 feats = torch.as_tensor(enc).to(device=eng.device, dtype=torch.float32)
                 segs += [(i, start, f) for (_, start, f) in self._plan(p[None], [feats], cfg, False)]
-        logits = eng.prefill_slots([p.to(eng.device) for p in prompts], segs, slots)
+        if past is None:
+            logits = eng.prefill_slots([p.to(eng.device) for p in prompts], segs, slots)
+        else:
+            logits = eng.prefill_slots([p.to(eng.device) for p in prompts], segs, slots, past=past)
         first = logits.argmax(-1)                                  # what generate() picks after the prompt
         self.ids[torch.tensor(slots, dtype=torch.long, device=eng.device)] = first
         return first.cpu().tolist()
@@ -195,17 +267,20 @@ class EngineSlots:
 
 @torch.no_grad()
 def generate_inflight(model, examples: Iterable[Sequence[Any]], slots: int = 8, max_new_tokens: int = 512,
-                      keywords: Sequence[str] = ("###",), tokenizer=None, trace: Optional[list] = None) -> Iterator[Tuple[int, torch.Tensor]]:
-    """Greedy generation with in-flight slot refill.  ``examples`` yields ``(prompt_ids, encoding[, max_new_tokens])`` with prompts
+                      keywords: Sequence[str] = ("###",), tokenizer=None, trace: Optional[list] = None,
+                      share_prefix: bool = False) -> Iterator[Tuple[int, torch.Tensor]]:
+    """Greedy generation with in-flight slot refill.  ``examples`` yields ``(prompt_ids, encoding[, max_new_tokens[, prefix_key]])`` with prompts
     of any length; up to ``slots`` of them decode together, each at its own KV-cache length, and a finished row's slot is refilled
     from the iterable (contiguous free slots prefilled as one batch) while the others keep decoding.  Stops per row as in
     :func:`generate_batch` (keyword -- needs ``tokenizer`` --, EOS or budget).  Yields ``(index, prompt + continuation ids)`` as
     examples complete.  ``model`` may provide ``slot_backend(n_slots)`` (any :class:`InflightScheduler` backend); otherwise its
-    engine's ragged slot mode serves it.  ``trace``: a list that receives the scheduler's events."""
+    engine's ragged slot mode serves it.  ``trace``: a list that receives the scheduler's events.  ``share_prefix``: examples with
+    equal ``prefix_key`` (the questions of one clip) share the K/V of their common leading tokens -- prefilled once, copied to the
+    siblings' slots, and read once per group by the decode step (:class:`InflightScheduler`, ``HipLlamaEngine.fork_slots``)."""
     if keywords and tokenizer is None:
         raise ValueError("generate_inflight: keyword stopping needs the tokenizer")
     make = getattr(model, "slot_backend", None)
-    backend = make(slots) if make is not None else EngineSlots(model, slots)
+    backend = make(slots) if make is not None else EngineSlots(model, slots, share_prefix)
     eos = getattr(getattr(model, "generation_config", None), "eos_token_id", None)
     stop_fn = None
     if keywords:
@@ -213,7 +288,7 @@ def generate_inflight(model, examples: Iterable[Sequence[Any]], slots: int = 8, 
             if row["stop"] is None:
                 row["stop"] = KeywordsStoppingCriteria(keywords=list(keywords), tokenizer=tokenizer, input_ids=row["prompt"][None])
             return bool(row["stop"](torch.cat((row["prompt"], gen))[None], None))
-    sched = InflightScheduler(backend, slots, max_new_tokens, eos, stop_fn)
+    sched = InflightScheduler(backend, slots, max_new_tokens, eos, stop_fn, share_prefix=share_prefix)
     if trace is not None:
         sched.trace = trace
     yield from sched.run(examples)
@@ -326,13 +401,15 @@ SHARD_COLUMNS = ["example_id", "prompt_text", "original_completion_text", "model
 
 def infer_from_shards(model, tokenizer, shards: str, multimodal_cfg: Dict[str, Any], end_seq: Sequence[int], outfile: Optional[str] = None,
                       slots: int = 8, max_samples: Optional[int] = None, max_new_tokens: int = 512, prompt: Optional[str] = None,
-                      seed: int = 0, allow_pickle: bool = False, header: str = DEFAULT_CONVERSATION_HEADER) -> List[Dict[str, str]]:
+                      seed: int = 0, allow_pickle: bool = False, header: str = DEFAULT_CONVERSATION_HEADER,
+                      share_prefix: bool = False) -> List[Dict[str, str]]:
     """Local tar shards -> CSV under the contract of ``scripts/inference/infer_from_webdataset.py:51-151``: every (question,
     answer) pair of a sample is one example whose prompt is its own human turn up to "### Assistant:" (audio placeholder first
     or last by a draw seeded with ``seed``); ``prompt`` overrides every question (the reference's ``--prompt``: audio first).
     Records ``example_id`` (the sample's tar key, repeated across its questions), ``prompt_text``, ``original_completion_text``
     (the pair's answer) and ``model_completion_text``, in input order.  ``max_samples`` caps the number of examples.  All
-    generation runs through :func:`generate_inflight` with ``slots`` batch slots."""
+    generation runs through :func:`generate_inflight` with ``slots`` batch slots.  ``share_prefix``: the questions of one sample
+    (its tar key is their ``prefix_key``) share the K/V of their common leading tokens when the audio placeholder comes first."""
     from .data import element_to_conversations, expand_urls, iter_tar_samples
 
     rng = random.Random(seed)
@@ -353,9 +430,10 @@ def infer_from_shards(model, tokenizer, shards: str, multimodal_cfg: Dict[str, A
                     prompt_text = prompt
                 meta.append({"example_id": conv["id"], "prompt_text": prompt_text,
                              "original_completion_text": tokenizer.decode(extract_response_tokens(ex["input_ids"], end_seq))})
-                yield ids, enc
+                yield ids, enc, None, conv["id"]
 
-    outs: Dict[int, torch.Tensor] = dict(generate_inflight(model, examples(), slots=slots, max_new_tokens=max_new_tokens, tokenizer=tokenizer))
+    outs: Dict[int, torch.Tensor] = dict(generate_inflight(model, examples(), slots=slots, max_new_tokens=max_new_tokens, tokenizer=tokenizer,
+                                                           share_prefix=share_prefix))
     records = []
     for i, m in enumerate(meta):
         records.append(dict(m, model_completion_text=tokenizer.decode(extract_response_tokens(outs[i], end_seq))))
@@ -441,6 +519,7 @@ def main_shards(argv=None):
     """``shards`` mode, with the flags of the reference's ``scripts/inference/infer_from_webdataset.py:154-190`` (+ ``--slots``):
     python -m llark_amd.m2t.infer_driver shards --model_name_or_path <dir> --eval_data_path "shards-{000000..000021}.tar" \
         --outfile results/infer.csv [--prompt "Describe ..."] [--max-samples N] [--max_new_tokens 2048] [--slots 8] [--allow-pickle]
+        [--share-prefix]
     ``--allow-pickle``: read ``.pyd`` (pickled) encodings -- unpickling runs code, pass it only for shards you trust."""
     import argparse
 
@@ -455,6 +534,8 @@ def main_shards(argv=None):
                     "--model_max_length positions: about 1 GiB per slot at 7B, 1024 positions, split precision)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--allow-pickle", action="store_true")
+    ap.add_argument("--share-prefix", action="store_true", help="the questions of one sample share the K/V of their common leading "
+                    "tokens (audio placeholder first): prefilled once, read once per group in the decode step")
     ap.add_argument("--mm_hidden_size", type=int, default=None)
     ap.add_argument("--model_max_length", type=int, default=2048)
     ap.add_argument("--llm-precision", default="split", choices=["split", "bf16"])
@@ -466,7 +547,7 @@ def main_shards(argv=None):
     model, tok, end_seq, mm_cfg = _load_for_inference(args, args.slots)
     recs = infer_from_shards(model, tok, args.eval_data_path, mm_cfg, end_seq, outfile=args.outfile, slots=args.slots,
                              max_samples=args.max_samples, max_new_tokens=args.max_new_tokens, prompt=args.prompt, seed=args.seed,
-                             allow_pickle=args.allow_pickle)
+                             allow_pickle=args.allow_pickle, share_prefix=args.share_prefix)
     print(f"writing {len(recs)} results to {args.outfile}")
     return recs
 

@@ -6,6 +6,7 @@ stream to the library.  There is no fallback: a missing library or a non-GPU ten
 """
 from __future__ import annotations
 
+import ctypes
 import os
 from typing import Optional, Tuple
 
@@ -982,6 +983,77 @@ def attn_decode_rope_rows(qkv: torch.Tensor, batch: int, nh: int, hd: int, pos_r
                                                           _opt(k_cache_lo, "k_cache_lo", bf), _opt(vt_cache_lo, "vt_cache_lo", bf), smax,
                                                           _dev(out, "out", bf), _opt(out_lo, "out_lo", bf),
                                                           _opt(alibi_slopes, "alibi_slopes", torch.float32), _stream()), "attn_decode_rope_rows")
+
+
+SHARED_GROUP_MEMBERS = 16                  # members per group of attn_decode_rope_shared (csrc/attn_shared.hip: GK_MEMBERS)
+SHARED_GROUP_STRIDE = 3 + SHARED_GROUP_MEMBERS          # int32 per group: source slot, shared length, members, member slots
+SHARED_STATUS = {1: "shared length is not a positive multiple of 8 (or exceeds smax)", 2: "a group must have 1 .. 16 members",
+                 3: "shared length greater than a member's position (or that member is idle / at smax)",
+                 4: "source slot inactive or shorter than the shared length", 5: "member slot out of range or slot_shared mismatch"}
+
+
+def kv_copy_prefix(k_cache: torch.Tensor, vt_cache: torch.Tensor, src: int, dst, n: int, k_cache_lo=None, vt_cache_lo=None) -> None:
+    """Positions [0, n) of cache slot ``src`` into every slot of ``dst`` (host ints), all layers and planes, one launch.  Whole caches:
+    k [layers][slots][nh][smax][128], v^T [layers][slots][nh][128][smax].  Writes up to round_up(n, 8) positions of V^T rows."""
+    bf = torch.bfloat16
+    assert k_cache.dim() == 5 and vt_cache.dim() == 5
+    layers, slots, nh, smax, hd = k_cache.shape
+    assert vt_cache.shape == (layers, slots, nh, hd, smax)
+    for c, ref in ((k_cache_lo, k_cache), (vt_cache_lo, vt_cache)):
+        assert c is None or c.shape == ref.shape
+    dst = [int(b) for b in dst]
+    arr = (ctypes.c_int * max(1, len(dst)))(*dst)
+    with _timed("kv_copy_prefix", 0.0):
+        check(_lib.lib().llark_kv_copy_prefix(_dev(k_cache, "k_cache", bf), _dev(vt_cache, "vt_cache", bf), _opt(k_cache_lo, "k_cache_lo", bf),
+                                              _opt(vt_cache_lo, "vt_cache_lo", bf), layers, slots, nh, hd, smax, int(src),
+                                              ctypes.cast(arr, ctypes.c_void_p), len(dst), int(n), _stream()), "kv_copy_prefix")
+
+
+def attn_decode_shared_scratch_bytes(batch: int, nh: int) -> int:
+    """Bytes of scratch :func:`attn_decode_rope_shared` needs (zero it once: its first word is the status of a refused table)."""
+    return int(_lib.lib().llark_attn_decode_shared_scratch_bytes(int(batch), int(nh)))
+
+
+def attn_decode_shared_status(scratch: torch.Tensor) -> int:
+    """Status word the kernels of :func:`attn_decode_rope_shared` leave in ``scratch`` (0 = no table refused; SHARED_STATUS names the
+    others).  Synchronises; clears the word."""
+    _dev(scratch, "scratch")
+    word = scratch.view(-1).view(torch.uint8)[:4].view(torch.int32)
+    code = int(word.item())
+    if code:
+        word.zero_()
+    return code
+
+
+def attn_decode_rope_shared(qkv: torch.Tensor, batch: int, nh: int, hd: int, pos_rows: torch.Tensor, cos_t, sin_t, k_cache, vt_cache, out,
+                            groups: Optional[torch.Tensor], slot_shared: torch.Tensor, scratch: torch.Tensor,
+                            k_cache_lo=None, vt_cache_lo=None, out_lo=None, check_table: bool = False) -> None:
+    """:func:`attn_decode_rope_rows` with shared prefixes: ``groups`` int32 [n_groups][SHARED_GROUP_STRIDE] = (source slot, shared
+    length P, members, member slots ...) and ``slot_shared`` int32 [batch] (P of the slot's group, 0 = none), both on the device.  The
+    members of a group read keys [0, P) once, from the source slot's cache.  ``scratch``: at least
+    :func:`attn_decode_shared_scratch_bytes` bytes, zeroed once.  The table is device data, so the kernel refuses a bad one through the
+    scratch's status word; ``check_table`` reads it back (a synchronisation) and raises."""
+    smax = k_cache.shape[-2]
+    bf = torch.bfloat16
+    assert qkv.shape == (batch, 3 * nh * hd) and pos_rows.numel() == batch and out.numel() == batch * nh * hd
+    assert k_cache.shape == (batch, nh, smax, hd) and vt_cache.shape == (batch, nh, hd, smax) and cos_t.shape == sin_t.shape
+    assert out_lo is None or out_lo.shape == out.shape
+    for c in (k_cache_lo, vt_cache_lo):
+        assert c is None or c.shape in (k_cache.shape, vt_cache.shape)
+    n_groups = 0 if groups is None else groups.shape[0]
+    assert groups is None or (groups.dim() == 2 and groups.shape[1] == SHARED_GROUP_STRIDE)
+    assert slot_shared.numel() == batch
+    with _timed("attn_decode_rope_shared", 0.0):
+        check(_lib.lib().llark_attn_decode_rope_bf16_shared(
+            _dev(qkv, "qkv", torch.float32), batch, nh, hd, _dev(pos_rows, "pos_rows", torch.int32), _dev(cos_t, "cos", torch.float32),
+            _dev(sin_t, "sin", torch.float32), cos_t.shape[0], _dev(k_cache, "k_cache", bf), _dev(vt_cache, "vt_cache", bf),
+            _opt(k_cache_lo, "k_cache_lo", bf), _opt(vt_cache_lo, "vt_cache_lo", bf), smax, _dev(out, "out", bf), _opt(out_lo, "out_lo", bf),
+            _opt(groups, "groups", torch.int32), n_groups, _dev(slot_shared, "slot_shared", torch.int32), _dev(scratch, "scratch"),
+            scratch.numel() * scratch.element_size(), _stream()), "attn_decode_rope_shared")
+    if check_table:
+        code = attn_decode_shared_status(scratch)
+        if code:
+            raise _lib.LlarkHipError(f"attn_decode_rope_shared: group table refused (status {code}): {SHARED_STATUS.get(code, '?')}")
 
 
 def decode_advance_rows(logits: Optional[torch.Tensor], state: torch.Tensor, next_ids: torch.Tensor, pos_rows: Optional[torch.Tensor] = None,

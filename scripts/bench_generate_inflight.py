@@ -15,6 +15,12 @@ per-kernel split of one step from ops kernel timing.  Prints ONE JSON line.
     python scripts/bench_generate_inflight.py [--slots 8,16,32,64] [--examples N] [--schedules batch1,grouped,inflight]
                                               [--precision split] [--seed 0]
 --examples defaults to 256 when a slot count above 16 is asked for (64 slots stay full for most of the run), 64 otherwise.
+
+    python scripts/bench_generate_inflight.py --slots 16,32,64 --questions-per-clip 1,4,8 --share-prefix
+Shared prompt prefixes: consecutive examples are the questions of one clip (one encoding, audio block first, one prefix key); every
+(slots, questions per clip) cell runs the inflight schedule with share_prefix off and on, alternating which goes first, and records
+clips/s, the decode step with every slot active, the attention launches' device time per step (ops kernel tags) and the time per
+example of filling the slots.  ONE JSON line on stdout (each cell also on stderr as it finishes).
 """
 import argparse
 import json
@@ -149,8 +155,108 @@ def decode_step_ms(model, examples, n_slots, steps=32):
     return ms, split
 
 
+def make_clip_examples(n: int, per_clip: int, seed: int):
+    """make_examples with `per_clip` consecutive examples per clip: one encoding, the audio block first (the shared prefix), a key,
+    and a question and budget of their own."""
+    g = torch.Generator().manual_seed(seed)
+    out = []
+    for i in range(n):
+        if i % per_clip == 0:
+            frames = 121 if int(torch.randint(0, 4, (1,), generator=g)) == 0 else 240
+            enc = torch.randn(frames, 4800, generator=g)
+            head = [1, BS.START] + [BS.PATCH] * frames + [BS.END]
+        text = int(torch.randint(8, 81, (1,), generator=g))
+        budget = int(torch.randint(16, 257, (1,), generator=g))
+        out.append((torch.tensor(head + torch.randint(3, 32000, (text,), generator=g).tolist()), enc, budget, f"clip{i // per_clip}"))
+    return out
+
+
+def run_inflight_keys(model, examples, slots, share):
+    trace = []
+    it = iter((ids, enc.cuda(), b, key) for ids, enc, b, key in examples)
+    outs = dict(generate_inflight(model, it, slots=slots, keywords=(), trace=trace, share_prefix=share))
+    return outs, sum(1 for e in trace if e[0] == "fork")
+
+
+def full_step(model, examples, n_slots, share, steps=32):
+    """Every slot active on the first n_slots examples (siblings forked from their clip's first example when `share`): ms per example
+    of filling the slots, wall-clock ms per decode step, device ms of the attention launches per step (ops kernel tags), groups."""
+    from llark_amd import ops
+    eng = model.engine
+    eng.init_slots(n_slots, share_prefix=share)
+    rows = examples[:n_slots]
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    ids = torch.zeros(n_slots, dtype=torch.int64, device="cuda")
+    lead = {}
+    full = [k for k, r in enumerate(rows) if not share or lead.setdefault(r[3], k) == k]
+    ids[full] = eng.prefill_slots([rows[k][0].cuda() for k in full], [(j, 1, rows[k][1].cuda()) for j, k in enumerate(full)], full).argmax(-1)
+    rest = [k for k in range(n_slots) if k not in full]
+    if rest:
+        past = [rows[k][1].shape[0] + 3 for k in rest]                   # <s> <audio_start> frames <audio_end>
+        for src in sorted(set(lead.values())):                            # one copy launch per clip: its siblings share one length
+            dsts = [k for k in rest if lead[rows[k][3]] == src]
+            if dsts:
+                eng.fork_slots(src, dsts, rows[src][1].shape[0] + 3)
+        ids[rest] = eng.prefill_slots([rows[k][0][p:].cuda() for k, p in zip(rest, past)], [], rest, past=past).argmax(-1)
+    torch.cuda.synchronize()
+    fill_ms = (time.perf_counter() - t0) / n_slots * 1e3
+    for _ in range(4):
+        ids, _, _ = eng.decode_slots(ids)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        ids, _, _ = eng.decode_slots(ids)
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) / steps * 1e3
+    ops.start_kernel_timing()
+    for _ in range(4):
+        ids, _, _ = eng.decode_slots(ids)
+    tags = ops.stop_kernel_timing()
+    attn = sum(v[1] for k, v in tags.items() if k in ("attn_decode_rope_rows", "attn_decode_rope_shared")) / 4
+    return {"prefill_ms_per_example": round(fill_ms, 3), "decode_step_ms": round(ms, 3), "attention_ms_per_step": round(attn, 3),
+            "groups": len(eng.group_list), "attention_tag": sorted(k for k in tags if k.startswith("attn_decode"))}
+
+
+def main_shared(args, slot_list):
+    """--questions-per-clip: the inflight schedule on clips with several questions each; with --share-prefix every cell runs twice in
+    this process, sharing off then on (the off run first in even cells, the on run first in odd ones)."""
+    qs = [int(x) for x in args.questions_per_clip.split(",") if x]
+    n_examples = args.examples if args.examples is not None else (256 if max(slot_list) > 16 else 64)
+    sets = {q: make_clip_examples(n_examples, q, args.seed) for q in qs}
+    max_seq = max(ids.numel() + b for ex in sets.values() for ids, _, b, _ in ex) + 8
+    model = RandomLlama(args.precision, max(slot_list), max_seq)
+    modes = [False, True] if args.share_prefix else [False]
+    for slots in slot_list:                                   # warm-up: every launch sequence once
+        for share in modes:
+            run_inflight_keys(model, [(i, e, 4, k) for i, e, _, k in sets[qs[-1]][: max(16, slots)]], slots, share)
+    res = {"bench": "generate_inflight_shared_prefix", "model": "llama2-7b dims, random weights", "precision": args.precision,
+           "examples": n_examples, "min_shared": model.engine.MIN_SHARED, "cells": []}
+    for c, (slots, q) in enumerate((s, q) for s in slot_list for q in qs):
+        ex = sets[q]
+        cell = {"slots": slots, "questions_per_clip": q, "generated_tokens": sum(e[2] for e in ex)}
+        outs = {}
+        for share in (modes if c % 2 == 0 else modes[::-1]):
+            (o, forks), t = timed(lambda: run_inflight_keys(model, ex, slots, share))
+            assert all(o[i].numel() == ex[i][0].numel() + ex[i][2] for i in range(len(ex)))
+            outs[share] = o
+            row = {"s": round(t, 3), "clips_per_s": round(len(ex) / t, 3), "forks": forks}
+            row.update(full_step(model, ex, slots, share))
+            cell["on" if share else "off"] = row
+        if len(modes) == 2:
+            cell["outputs_equal"] = sum(torch.equal(outs[True][i].cpu(), outs[False][i].cpu()) for i in range(len(ex)))
+            cell["on_over_off"] = {k: round(cell["on"][k] / cell["off"][k], 4)
+                                   for k in ("clips_per_s", "decode_step_ms", "attention_ms_per_step", "prefill_ms_per_example")}
+        res["cells"].append(cell)
+        print(json.dumps(cell), file=sys.stderr, flush=True)
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--questions-per-clip", default=None, help="e.g. 1,4,8: consecutive examples share an encoding, an audio-first prefix "
+                    "and a prefix key (inflight schedule only; one result cell per slot count and value)")
+    ap.add_argument("--share-prefix", action="store_true", help="with --questions-per-clip: run every cell with share_prefix off and on")
     ap.add_argument("--slots", default="8,16,32,64", help="slot counts of the inflight schedule, 1 .. 64 each")
     ap.add_argument("--examples", type=int, default=None, help="default: 256 with a slot count above 16, else 64")
     ap.add_argument("--schedules", default="batch1,grouped,inflight", help="which schedules to time")
@@ -162,6 +268,10 @@ def main():
     slot_list = [int(x) for x in args.slots.split(",") if x]
     if not slot_list or any(not 1 <= n <= 64 for n in slot_list):
         ap.error(f"--slots takes counts in 1 .. 64, got {args.slots!r}")
+    if args.questions_per_clip:
+        return main_shared(args, slot_list)
+    if args.share_prefix:
+        ap.error("--share-prefix needs --questions-per-clip")
     schedules = set(args.schedules.split(","))
     n_examples = args.examples if args.examples is not None else (256 if max(slot_list) > 16 else 64)
     step_slots = [n for n in (1, 8, 16, 32, 48, 64) if n <= max(16, max(slot_list))]
