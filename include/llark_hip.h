@@ -163,10 +163,19 @@ int llark_prior_embed(const int64_t* z, int n, int t, int width, int bins, const
 int llark_prior_head(const int64_t* z, int n, int t, int width, int bins, const float* x_emb, const float* pos_emb,
                      const float* x_cond, const float* y_cond, const float* gamma, const float* beta, float eps, float* h,
                      void* out_hi, void* out_lo, int ldo, float* pred, llark_stream_t stream);
-/* LayerNorm(width, eps) in fp32 -> fp16 hi/lo planes [rows][ldo] */
+/* LayerNorm(width, eps) in fp32 -> fp16 hi/lo planes [rows][ldo].  width % 4 == 0, width <= 8192.
+ * Precision of an fp16 hi/lo pair, here and wherever this header speaks of "22 bits" or "fp32-class": hi = fp16(x), lo = fp16(x - hi) is
+ * within 2^-22 |x| of x only while lo is a NORMAL fp16, |x - hi| >= 2^-14, which |x| >= 2^-3 guarantees.  Below that lo is subnormal with
+ * a spacing of 2^-24 and the pair carries an ABSOLUTE error of up to 2^-25 whatever |x| is:  |x - hi - lo| <= 2^-22 |x| + 2^-25.
+ * (|x| > 65504 overflows the hi plane.)  Producers that must keep 22 bits on small values scale by a power of two first: llark_gemm16_ln_p. */
 int llark_layernorm_split_f16(const float* x, int ldx, int rows, int width, const float* gamma, const float* beta,
                               float eps, void* out_hi, void* out_lo, int ldo, llark_stream_t stream);
-/* FactoredAttention core (pattern 1 block, 2 transpose-block, 3 previous-block) on qkv [n*t][ldq]. */
+/* FactoredAttention core (pattern 1 block, 2 transpose-block, 3 previous-block) on qkv [n*t][ldq] -> fp16 hi/lo planes [n*t][ldo].
+ * q, k, v, the probabilities and the output are each carried as an fp16 hi/lo pair (three MFMA passes per product, lo.lo dropped), with
+ * the precision stated above: softmax probabilities are almost always below 2^-3, so next to the relative 2^-22 terms every output
+ * element carries a floor of  2^-25 (2 + sum_visible |v_jd|) + 2 B 2^-25 / sqrt(hd) max_j sum_d (|q_d| + |k_jd|),  B = sum_j p_j |v_jd|
+ * (tests/prior_kernel_ref.py derives and measures it).  head_dim = n_state / heads even and <= 160, block_ctx = t / blocks <= 64,
+ * blocks <= 64 or == 128, ldq >= 3 n_state and ldo >= n_state both even; LLARK_ERR_* before anything is launched otherwise. */
 int llark_prior_attn(const float* qkv, int ldq, int n, int t, int n_state, int heads, int blocks, int pattern,
                      void* out_hi, void* out_lo, int ldo, llark_stream_t stream);
 /* The same two producers in "lo8" mode (see llark_gemm16_lo8): fp16 hi plane [rows][ldo] + E4M3 low plane
@@ -228,7 +237,8 @@ int llark_ln_stats_finalize(const float* part, int rows, int nparts, int width, 
 /* Round 5: the producer role with PREDICTED row statistics.  ln_pred [m][2] = (shift_m, scale_m), scale a power of two: out_hi / out_lo then
  * hold hi / lo of ((c - shift_m) scale_m) ln_vec[n] -- values of order one, so that rows whose level is far from their spread (|mean| >> std)
  * or whose spread is far from one (std ~ 1e-3: the fp16 lo plane would sit in its subnormals; std ~ 1e3: the hi plane would overflow) keep the
- * planes' 22 bits -- and ln_part the sums of (c - shift_m) and of its square.  llark_ln_stats_finalize_p reduces them to the pair the
+ * planes' 22 bits (an fp16 hi/lo pair has them for |x| >= 2^-3 only: see llark_layernorm_split_f16) -- and ln_part the sums of
+ * (c - shift_m) and of its square.  llark_ln_stats_finalize_p reduces them to the pair the
  * UNCHANGED consumer role applies, ln_stat = ((mean - shift) scale, rstd / scale), and replaces ln_pred by the prediction for the next
  * LayerNorm of the same rows, (mean, nearest power of two of rstd).  llark_ln_row_pred makes the first prediction of a forward from the rows
  * of x themselves.  ln_pred = NULL: llark_gemm16_ln.  Same call sites (upstream ResAttnBlock ln_0 / ln_1 around the Conv1D products). */

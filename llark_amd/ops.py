@@ -362,8 +362,8 @@ def prior_head(z, x_emb, pos_emb, x_cond, y_cond, gamma, beta, eps: float, out_h
 def layernorm_split(x: torch.Tensor, gamma, beta, eps: float, out_hi: torch.Tensor, out_lo: torch.Tensor) -> None:
     """x [rows][width] fp32 -> fp16 hi/lo planes [rows][ldo]."""
     rows, width = x.shape
-    assert out_hi.shape == out_lo.shape and out_hi.shape[0] == rows and out_hi.shape[1] >= width
-    check(_lib.lib().llark_layernorm_split_f16(_dev(x, "x", torch.float32), x.stride(0), rows, width,
+    assert out_hi.shape == out_lo.shape and out_hi.shape[0] == rows and out_hi.shape[1] >= width and x.stride(1) == 1
+    check(_lib.lib().llark_layernorm_split_f16(_dev(x, "x", torch.float32, contiguous=False), x.stride(0), rows, width,
                                                _dev(gamma, "gamma", torch.float32), _dev(beta, "beta", torch.float32),
                                                float(eps), _dev(out_hi, "out_hi", torch.float16),
                                                _dev(out_lo, "out_lo", torch.float16), out_hi.stride(0), _stream()),
@@ -373,8 +373,8 @@ def layernorm_split(x: torch.Tensor, gamma, beta, eps: float, out_hi: torch.Tens
 def layernorm_split_lo8(x: torch.Tensor, gamma, beta, eps: float, out_hi: torch.Tensor, out_lo8: torch.Tensor, sa: int = LO8_SA) -> None:
     """x [rows][width] fp32 -> fp16 hi plane [rows][ldo] + E4M3 low plane [rows][ldo8] (uint8, MFMA slot order)."""
     rows, width = x.shape
-    assert out_hi.shape[0] == rows and out_lo8.shape[0] == rows and out_hi.shape[1] >= width and out_lo8.dtype == torch.uint8
-    check(_lib.lib().llark_layernorm_split_lo8(_dev(x, "x", torch.float32), x.stride(0), rows, width,
+    assert out_hi.shape[0] == rows and out_lo8.shape[0] == rows and out_hi.shape[1] >= width and out_lo8.dtype == torch.uint8 and x.stride(1) == 1
+    check(_lib.lib().llark_layernorm_split_lo8(_dev(x, "x", torch.float32, contiguous=False), x.stride(0), rows, width,
                                                _dev(gamma, "gamma", torch.float32), _dev(beta, "beta", torch.float32),
                                                float(eps), _dev(out_hi, "out_hi", torch.float16), out_hi.stride(0),
                                                _dev(out_lo8, "out_lo8", torch.uint8), out_lo8.stride(0), int(sa), _stream()),
@@ -436,6 +436,13 @@ def pool_mean(h: torch.Tensor, lens: Optional[torch.Tensor] = None) -> torch.Ten
     check(_lib.lib().llark_pool_mean(_dev(h, "h", torch.float32), n, t, width, _opt(lens, "lens", torch.int32), _dev(out, "out"),
                                      _stream()), "pool_mean")
     return out
+
+
+def zero_pad16(plane: torch.Tensor, from_col: int) -> None:
+    """zero the columns [from_col, ld) of a 16-bit plane [rows][ld] (the K padding of a GEMM operand)"""
+    rows, ld = plane.shape
+    assert plane.element_size() == 2
+    check(_lib.lib().llark_zero_pad16(_dev(plane, "plane"), rows, ld, int(from_col), _stream()), "zero_pad16")
 
 
 # ------------------------------------------------------------------------------------------------
@@ -625,8 +632,8 @@ def ln_row_pred(x: torch.Tensor, eps: float, pred: torch.Tensor) -> None:
     """pred [rows][2] = (mean, nearest power of two of 1 / sqrt(var + eps)) of the rows of x (fp32 [rows][width]): the first prediction
     of a forward for the producers of :func:`gemm16_ln` (ln_pred)."""
     rows, width = x.shape
-    assert pred.numel() >= 2 * rows and pred.is_contiguous()
-    check(_lib.lib().llark_ln_row_pred(_dev(x, "x", torch.float32), x.stride(0), rows, width, float(eps), _dev(pred, "pred", torch.float32),
+    assert pred.numel() >= 2 * rows and pred.is_contiguous() and x.stride(1) == 1
+    check(_lib.lib().llark_ln_row_pred(_dev(x, "x", torch.float32, contiguous=False), x.stride(0), rows, width, float(eps), _dev(pred, "pred", torch.float32),
                                        _stream()), "ln_row_pred")
 
 

@@ -45,7 +45,7 @@ def check(name, got, ref64, atol, rtol=0.0, bound=None, r_torch=None, under=None
 
 
 def bits(t):
-    return t.detach().cpu().contiguous().view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+    return t.detach().cpu().contiguous().view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
 
 
 def nan_buf(rows, ld):
@@ -54,6 +54,18 @@ def nan_buf(rows, ld):
 
 def bf_sentinel(shape):
     return torch.full(shape, BF_SENTINEL, dtype=torch.int16).view(torch.bfloat16)
+
+
+F16_SENTINEL = 0x7DB5           # an fp16 NaN with a recognisable payload
+U8_SENTINEL = 0xA5
+
+
+def f16_sentinel(shape):
+    return torch.full(shape, F16_SENTINEL, dtype=torch.int16).view(torch.float16)
+
+
+def u8_sentinel(shape):
+    return torch.full(shape, U8_SENTINEL, dtype=torch.uint8)
 
 
 def assert_untouched(name, after, before, written):
