@@ -124,7 +124,8 @@ int llark_vqvae_encode(void* plan, const float* audio, int n, int t, float* buf0
  *   output: planes out_hi / out_lo [n][tin/2][C] and / or out_f32 [n][C][tin/2], C = 64 with the output conv else 32.
  *   wexp  : HOST array of 2 + 2 depth ints: the exp2 each weight tensor was packed with (strided conv; dilated conv, 1x1 per block;
  *           output conv; 0 where a tensor is not fragment-packed).
- * tin even; sum(dil) (+1 with the output conv) <= 48. */
+ * tin even; 1 <= depth <= 4; sum(dil) (+1 with the output conv) <= 48 (the window's halo) and each dilation <= 32 (the zero guard
+ * rows a tap may reach beyond the window; LLARK_ERR_UNSUPPORTED above that). */
 int llark_vqvae_stage_f16x2(const float* audio, const void* in_hi, const void* in_lo, int n, int cin, int tin, const float* w0_f32,
                             const void* w0_hi, const void* w0_lo, const float* b0, const void* wr_hi, const void* wr_lo,
                             const float* br, int depth, const int* dil, const void* wo_hi, const void* wo_lo, const float* bo,

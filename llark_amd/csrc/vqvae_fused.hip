@@ -33,6 +33,7 @@ namespace llark {
 constexpr int VF_ROW = 144;            // LDS bytes per position
 constexpr int VF_HALO = 48;            // positions of halo on each side of a window (>= 1 + 3 + 9 + 27 + 1)
 constexpr int VF_MAXDEPTH = 4;
+constexpr int VF_GUARD = 32;           // zero LDS rows on either side of a window = the largest dilation a fragment read may reach over
 
 struct VqStageParams {
     const float* audio;                // CIN == 1: [n][tin] fp32
@@ -88,7 +89,8 @@ __device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned&
 template <int CIN, bool OUTCONV, int NTW>
 __global__ __launch_bounds__(512, 2) void vq_stage_kernel(const VqStageParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    constexpr int GUARD = 32;                                       // zero rows on either side of the window: no bounds checks on fragment reads
+    constexpr int GUARD = VF_GUARD;                                 // zero rows on either side of the window: no bounds checks on fragment reads
+                                                                    // (rows pos +- dil[i]: the launcher refuses dil[i] > VF_GUARD)
     char* const smem = smem_raw + GUARD * VF_ROW;                   // row 0 = window position 0
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -363,7 +365,7 @@ template <int CIN, bool OUTCONV, int NTW>
 static int launch_vq_stage_n(const VqStageParams& p, hipStream_t s) {
     auto kern = vq_stage_kernel<CIN, OUTCONV, NTW>;
     constexpr int P = NTW * 8 * 32;
-    constexpr int lds = (P + 64) * VF_ROW;
+    constexpr int lds = (P + 2 * VF_GUARD) * VF_ROW;
     static_assert(lds <= 160 * 1024, "window + guard rows must fit the LDS");
     static PerDeviceOnce once;                  // per device: the attribute belongs to the device's function object
     if (once.first()) {
@@ -388,7 +390,8 @@ using namespace llark;
 
 // One fused stage of the VQ-VAE encoder (see the header of this file).  Weight operands are the fragment-major fp16 hi / lo copies
 // llark_vqvae_pack_frag16 makes at load time.  cin: 1 (audio fp32 [n][tin]), 32 or 64 (planes in_hi / in_lo [n][tin][cin]).
-// depth <= 4 residual blocks with dilations dil[0 .. depth); their sum (+1 with the output conv) must fit the 48-position halo.
+// depth <= 4 residual blocks with dilations dil[0 .. depth); their sum (+1 with the output conv) must fit the 48-position halo and
+// each of them the 32 guard rows of the LDS window (LLARK_ERR_UNSUPPORTED otherwise).
 // wexp (HOST array, 2 + 2 depth ints): the power-of-two exponents the weight tensors were packed with (llark_vqvae_pack_frag16's
 // `exp2`), in the order strided conv, (dilated conv, 1x1) per block, output conv; 0 for tensors that are not fragment-packed.
 // Outputs (either or both): planes out_hi / out_lo [n][tin/2][C], fp32 out_f32 [n][C][tin/2]; C = 64 with the output conv else 32.
@@ -407,6 +410,10 @@ extern "C" int llark_vqvae_stage_f16x2(const float* audio, const void* in_hi, co
     int halo = wo_hi ? 1 : 0;
     for (int i = 0; i < depth; ++i) {
         LLARK_REQUIRE(dil[i] >= 1, "vqvae_stage: dilation %d", dil[i]);
+        if (dil[i] > VF_GUARD) {        // a tap at pos +- dil[i] would leave the window's guard rows: below the LDS allocation and past its end
+            set_error("vqvae_stage: dilation dil[%d] = %d exceeds the %d guard rows of the LDS window", i, dil[i], VF_GUARD);
+            return LLARK_ERR_UNSUPPORTED;
+        }
         p.dil[i] = dil[i];
         halo += dil[i];
     }
