@@ -701,6 +701,16 @@ int llark_attn_backward_bf16_varlen(const void* q, const void* k_cache, const vo
 int llark_attn_backward_bf16_fused_varlen(const void* q, const void* k_cache, const void* v_rm, const void* dO, int ld_do, const void* o,
                                           const float* lse, float* dsum, const int* seqs, int nseq, int max_len, int s_total, int nh, int hd,
                                           int smax, const float* cos_t, const float* sin_t, int max_pos, void* dqkv, llark_stream_t stream);
+/* The variable-length training pair with ALiBi (MPT): the same contract as llark_attn_prefill_bf16_lse_varlen / llark_attn_backward_bf16_varlen
+ * plus alibi_slopes fp32 [nh] (null: LLARK_ERR_INVALID).  The bias of sequence b is slope_h * (i - (len_b - 1)) with i the key's position
+ * INSIDE the sequence, so out, lse, dsum, dq, dk, dv are bit-equal, sequence by sequence, to llark_attn_prefill_bf16_lse /
+ * llark_attn_backward_bf16 called with the same slopes at batch = 1, s = len_b (below the uniform call's 128-query-block threshold). */
+int llark_attn_prefill_bf16_lse_varlen_alibi(const void* q, const void* k_cache, const void* vt_cache, const int* seqs, int nseq, int max_len,
+                                             int s_total, int nh, int hd, int smax, void* out, float* lse, const float* alibi_slopes,
+                                             llark_stream_t stream);
+int llark_attn_backward_bf16_varlen_alibi(const void* q, const void* k_cache, const void* v_rm, const void* dO, const void* o, const float* lse,
+                                          float* dsum, const int* seqs, int nseq, int max_len, int s_total, int nh, int hd, int smax, float* dq,
+                                          float* dk, float* dv, const float* alibi_slopes, llark_stream_t stream);
 /* dW = dY^T . X without transposed copies of dY (csrc/gemm_bda.hip, round 6; torch autograd of nn.Linear: grad_weight = grad_output^T .
  * input, under WrappedLlamav2ForCausalLM.forward + loss.backward(), m2t/models/llamav2.py:259-337, m2t/train.py:53-277):
  *   llark_pack_frag_t16: src [kp][ld] 16-bit (row = contraction index: the token; column = feature) -> dst = the fragment-major copy of

@@ -660,9 +660,10 @@ static int attn_backward_impl(const void* q, const void* k_cache, const void* v_
 // np(max_len) * nseq * nh workgroups, those beyond their own sequence's tile count return -- and the tiles go in pairs when the SUMMED tile
 // count fills the chip as a uniform launch of that many tiles would.  The table lives on the device, so the sum is taken as
 // cdiv(s_total, 64): the ranges are disjoint, which puts the true sum between that and that + nseq.
+template <bool ALIBI>
 static int attn_backward_varlen_impl(const void* q, const void* k_cache, const void* v_rm, const void* dO, const void* o, const float* lse, float* dsum,
                                      const int* seqs, int nseq, int max_len, int s_total, int nh, int smax, float* dq, float* dk, float* dv,
-                                     const AttnBwdFused& f, llark_stream_t stream) {
+                                     const float* alibi, const AttnBwdFused& f, const char* name, llark_stream_t stream) {
     const float scale = (float)(1.0 / sqrt(128.0));
     hipStream_t st = (hipStream_t)stream;
     const AttnSeqs<true> vl = {seqs, s_total};
@@ -674,13 +675,13 @@ static int attn_backward_varlen_impl(const void* q, const void* k_cache, const v
     const int paired = nt >= 2 && (wgs >= 2048 || wgs == 512 || wgs == 1024);
     const int grid = (paired ? (nt + 1) / 2 : nt) * nbh;
     const int lds_kv = 2 * (32768 + 512), lds_q = 2 * 32768;
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<DKV_NK, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_kv);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<DQ_NQ, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_q);
-    attn_bwd_dkv_kernel<DKV_NK, false, true><<<grid, 256, lds_kv, st>>>((const bf16_t*)q, (const bf16_t*)k_cache, (const bf16_t*)v_rm, (const bf16_t*)dO, lse,
-                                                                        dsum, dk, dv, max_len, smax, nbh, nh, scale, nullptr, f, paired, vl);
-    attn_bwd_dq_kernel<DQ_NQ, false, true><<<grid, 256, lds_q, st>>>((const bf16_t*)q, (const bf16_t*)k_cache, (const bf16_t*)v_rm, (const bf16_t*)dO, lse, dsum,
-                                                                     dq, max_len, smax, nbh, nh, scale, nullptr, f, paired, vl);
-    return check_launch("attn_backward_varlen");
+    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<DKV_NK, ALIBI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_kv);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<DQ_NQ, ALIBI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_q);
+    attn_bwd_dkv_kernel<DKV_NK, ALIBI, true><<<grid, 256, lds_kv, st>>>((const bf16_t*)q, (const bf16_t*)k_cache, (const bf16_t*)v_rm, (const bf16_t*)dO, lse,
+                                                                        dsum, dk, dv, max_len, smax, nbh, nh, scale, alibi, f, paired, vl);
+    attn_bwd_dq_kernel<DQ_NQ, ALIBI, true><<<grid, 256, lds_q, st>>>((const bf16_t*)q, (const bf16_t*)k_cache, (const bf16_t*)v_rm, (const bf16_t*)dO, lse, dsum,
+                                                                     dq, max_len, smax, nbh, nh, scale, alibi, f, paired, vl);
+    return check_launch(name);
 }
 
 // llark_attn_backward_bf16 over the sequences of a device table seqs [nseq][2] = (off, len) (include/llark_hip.h): batch = 1, s = s_total.
@@ -691,7 +692,22 @@ extern "C" int llark_attn_backward_bf16_varlen(const void* q, const void* k_cach
     ATTN_VARLEN_REQUIRE_SHAPE("attn_backward_varlen");
     AttnBwdFused f = {};
     f.ld_do = 128;
-    return attn_backward_varlen_impl(q, k_cache, v_rm, dO, o, lse, dsum, seqs, nseq, max_len, s_total, nh, smax, dq, dk, dv, f, stream);
+    return attn_backward_varlen_impl<false>(q, k_cache, v_rm, dO, o, lse, dsum, seqs, nseq, max_len, s_total, nh, smax, dq, dk, dv, nullptr, f,
+                                            "attn_backward_varlen", stream);
+}
+
+// The same with ALiBi (MPT): the ALIBI instantiations of the same kernels, slopes fp32 [nh] as given to llark_attn_prefill_bf16_lse_varlen_alibi.
+// P is recomputed from that forward's lse, so the bias is the forward's: slope_h * (i_key - (len_b - 1)), positions inside the sequence.
+extern "C" int llark_attn_backward_bf16_varlen_alibi(const void* q, const void* k_cache, const void* v_rm, const void* dO, const void* o,
+                                                     const float* lse, float* dsum, const int* seqs, int nseq, int max_len, int s_total, int nh,
+                                                     int hd, int smax, float* dq, float* dk, float* dv, const float* alibi_slopes,
+                                                     llark_stream_t stream) {
+    LLARK_REQUIRE(q && k_cache && v_rm && dO && o && lse && dsum && seqs && dq && dk && dv && alibi_slopes, "attn_backward_varlen_alibi: null pointer");
+    ATTN_VARLEN_REQUIRE_SHAPE("attn_backward_varlen_alibi");
+    AttnBwdFused f = {};
+    f.ld_do = 128;
+    return attn_backward_varlen_impl<true>(q, k_cache, v_rm, dO, o, lse, dsum, seqs, nseq, max_len, s_total, nh, smax, dq, dk, dv, alibi_slopes, f,
+                                           "attn_backward_varlen_alibi", stream);
 }
 
 // llark_attn_backward_bf16_fused over the sequences of a table; the RoPE backward of row off + i uses position i (max_len <= max_pos).
@@ -704,7 +720,8 @@ extern "C" int llark_attn_backward_bf16_fused_varlen(const void* q, const void* 
     LLARK_REQUIRE(ld_do >= nh * 128 && ld_do % 8 == 0 && ((uintptr_t)dO & 15) == 0 && ((uintptr_t)dqkv & 7) == 0, "attn_backward_fused_varlen: dO must be [s_total][ld_do >= nh*128], ld_do %% 8 == 0, 16-byte aligned");
     AttnBwdFused f = {};
     f.ld_do = ld_do; f.dqkv = (bf16_t*)dqkv; f.cos_t = cos_t; f.sin_t = sin_t; f.pos0 = 0;
-    return attn_backward_varlen_impl(q, k_cache, v_rm, dO, o, lse, dsum, seqs, nseq, max_len, s_total, nh, smax, nullptr, nullptr, nullptr, f, stream);
+    return attn_backward_varlen_impl<false>(q, k_cache, v_rm, dO, o, lse, dsum, seqs, nseq, max_len, s_total, nh, smax, nullptr, nullptr, nullptr, nullptr,
+                                            f, "attn_backward_varlen", stream);
 }
 
 extern "C" int llark_attn_backward_bf16(const void* q, const void* k_cache, const void* v_rm, const void* dO, const void* o,

@@ -1113,20 +1113,38 @@ extern "C" int llark_attn_prefill_bf16_lse(const void* q, const void* k_cache, c
 // the 64-query instantiation.  The grid is sized for max_len: np(max_len) * nseq * nh workgroups, those beyond their own sequence's block
 // count return.  Blocks go in pairs when the summed block count -- taken as cdiv(s_total, 64): the table lives on the device, the ranges are
 // disjoint, so the true sum lies between that and that + nseq -- fills the chip as a uniform launch of that many blocks would.
+template <bool ALIBI>
+static void launch_attn_prefill_varlen(hipStream_t st, const void* q, const void* k_cache, const void* vt_cache, const int* seqs, int nseq, int max_len,
+                                       int s_total, int nh, int smax, void* out, float* lse, const float* alibi) {
+    const int lds = 65536, nbh = nseq * nh, nt = cdiv(max_len, 64);
+    const long wgs = (long)((cdiv(s_total, 64) + 1) / 2) * nh;
+    const int pr = nt >= 2 && (wgs >= 2048 || wgs == 512 || wgs == 1024);
+    static PerDeviceOnce once;                                      // per (instantiation, device)
+    if (once.first()) (void)hipFuncSetAttribute((const void*)attn_prefill_kernel<false, 1, false, ALIBI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    const AttnSeqs<true> vl = {seqs, s_total};
+    attn_prefill_kernel<false, 1, false, ALIBI, true><<<(pr ? (nt + 1) / 2 : nt) * nbh, 256, lds, st>>>(
+        (const bf16_t*)q, (const bf16_t*)k_cache, (const bf16_t*)vt_cache, nullptr, nullptr, nullptr, (bf16_t*)out, nullptr, max_len, nh, nbh, 0, smax,
+        (float)(1.0 / sqrt(128.0)), alibi, lse, pr, vl);
+}
+
 extern "C" int llark_attn_prefill_bf16_lse_varlen(const void* q, const void* k_cache, const void* vt_cache, const int* seqs, int nseq, int max_len,
                                                   int s_total, int nh, int hd, int smax, void* out, float* lse, llark_stream_t stream) {
     LLARK_REQUIRE(q && k_cache && vt_cache && seqs && out && lse, "attn_prefill_lse_varlen: null pointer");
     ATTN_VARLEN_REQUIRE_SHAPE("attn_prefill_lse_varlen");
-    const int lds = 65536, nbh = nseq * nh, nt = cdiv(max_len, 64);
-    const long wgs = (long)((cdiv(s_total, 64) + 1) / 2) * nh;
-    const int pr = nt >= 2 && (wgs >= 2048 || wgs == 512 || wgs == 1024);
-    static PerDeviceOnce once;
-    if (once.first()) (void)hipFuncSetAttribute((const void*)attn_prefill_kernel<false, 1, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    const AttnSeqs<true> vl = {seqs, s_total};
-    attn_prefill_kernel<false, 1, false, false, true><<<(pr ? (nt + 1) / 2 : nt) * nbh, 256, lds, (hipStream_t)stream>>>(
-        (const bf16_t*)q, (const bf16_t*)k_cache, (const bf16_t*)vt_cache, nullptr, nullptr, nullptr, (bf16_t*)out, nullptr, max_len, nh, nbh, 0, smax,
-        (float)(1.0 / sqrt((double)hd)), nullptr, lse, pr, vl);
+    launch_attn_prefill_varlen<false>((hipStream_t)stream, q, k_cache, vt_cache, seqs, nseq, max_len, s_total, nh, smax, out, lse, nullptr);
     return check_launch("attn_prefill_lse_varlen");
+}
+
+// The same with ALiBi (MPT): the ALIBI instantiation of the same kernel.  The bias of sequence b is slope_h * (i_key - (len_b - 1)) with
+// i_key the key's position INSIDE the sequence -- the kernel's S and key indices are the sequence's own after the prologue -- so lse is
+// that of the uniform call with batch = 1, s = len_b, which is what the backward recomputes P from.  Head = bhid % nh, sequence = bhid / nh.
+extern "C" int llark_attn_prefill_bf16_lse_varlen_alibi(const void* q, const void* k_cache, const void* vt_cache, const int* seqs, int nseq,
+                                                        int max_len, int s_total, int nh, int hd, int smax, void* out, float* lse,
+                                                        const float* alibi_slopes, llark_stream_t stream) {
+    LLARK_REQUIRE(q && k_cache && vt_cache && seqs && out && lse && alibi_slopes, "attn_prefill_lse_varlen_alibi: null pointer");
+    ATTN_VARLEN_REQUIRE_SHAPE("attn_prefill_lse_varlen_alibi");
+    launch_attn_prefill_varlen<true>((hipStream_t)stream, q, k_cache, vt_cache, seqs, nseq, max_len, s_total, nh, smax, out, lse, alibi_slopes);
+    return check_launch("attn_prefill_lse_varlen_alibi");
 }
 
 extern "C" int llark_attn_prefill_bf16(const void* q, const void* k_cache, const void* vt_cache, const void* q_lo,

@@ -13,6 +13,9 @@ LoRA runs (``--lora_enable True``, m2t/train.py:264-273) write adapters instead 
 ``adapter_model.bin`` (peft names, unpadded rank), ``adapter_config.json``, ``non_lora_trainables.bin`` (``mm_projector`` and
 ``embed_tokens``, the trainable tensors that are not adapters) and ``trainer_state.pt`` -- and no ``pytorch_model.bin``.
 
+An MPT trainer (``HipMptTrainer``) writes the same files under the reference's MPT names (``transformer.blocks.N.attn.Wqkv.weight`` ...
+``transformer.mm_projector.{weight,bias}``, the tied ``transformer.wte.weight``): ``WrappedMPTForCausalLM.from_pretrained`` opens the folder.
+
 Added for exact resumption (the reference relies on HF Trainer's optimizer.pt / scheduler.pt / trainer_state.json): the
 fp32 AdamW moments and the step counter in ``trainer_state.pt`` (kernel layout, one flat tensor each).
 """
@@ -50,6 +53,12 @@ def adapter_state(state_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor
     return {k: v for k, v in state_dict.items() if any(m in k for m in ADAPTER_KEYS)}
 
 
+def engine_state(eng) -> Dict[str, torch.Tensor]:
+    """The engine's weights under the reference's names, as views of the kernel-layout tensors: ``state_dict_hf`` of the Llama engine,
+    ``state_dict`` of the MPT engine."""
+    return eng.state_dict_hf() if hasattr(eng, "state_dict_hf") else eng.state_dict()
+
+
 def save_checkpoint(trainer, output_dir: str, save_total_limit: Optional[int] = 1, rank: int = 0, hf_config=None,
                     tokenizer=None) -> Optional[str]:
     """Writes ``checkpoint-<trainer.step_count>`` (+ the adapter side-file) from rank 0; other ranks return None.
@@ -73,13 +82,14 @@ def save_checkpoint(trainer, output_dir: str, save_total_limit: Optional[int] = 
         sd = {k: v.detach().cpu().contiguous() for k, v in adapter_state(trainer.eng.state_dict_hf()).items()}
         torch.save(sd, os.path.join(tmp, LO.NON_LORA_TRAINABLES))
     else:
-        sd = {k: v.detach().cpu().contiguous() for k, v in trainer.eng.state_dict_hf().items()}
+        sd = {k: v.detach().cpu().contiguous() for k, v in engine_state(trainer.eng).items()}
         torch.save(sd, os.path.join(tmp, "pytorch_model.bin"))
     torch.save({"step": step, "lr": trainer.lr, "betas": trainer.betas, "eps": trainer.eps, "weight_decay": trainer.wd,
                 "exp_avg": trainer.flat_m.cpu(), "exp_avg_sq": trainer.flat_v.cpu(),
                 "param_order": [n for n, _ in trainer.params]}, os.path.join(tmp, "trainer_state.pt"))
     if hf_config is not None:
-        hf_config.vocab_size = int(sd["model.embed_tokens.weight"].shape[0])
+        table = "model.embed_tokens.weight" if "model.embed_tokens.weight" in sd else "transformer.wte.weight"
+        hf_config.vocab_size = int(sd[table].shape[0])
         hf_config.save_pretrained(tmp)
     if tokenizer is not None:
         tokenizer.save_pretrained(tmp)
@@ -98,7 +108,8 @@ def save_checkpoint(trainer, output_dir: str, save_total_limit: Optional[int] = 
 def copy_weights_into_engine(eng, sd: Dict[str, torch.Tensor], origin: str = "state dict") -> None:
     """Copies HF-named weights into the engine's kernel-layout tensors IN PLACE (views from ``state_dict_hf``), so that
     whatever points at those tensors (a trainer's parameter table, recorded launch lists) stays valid."""
-    cur = eng.state_dict_hf()
+    cur = engine_state(eng)
+    llama = hasattr(eng, "layers")                            # (the MPT engine stores every tensor as the reference lays it out)
     missing = [k for k in cur if k not in sd]
     if missing:
         raise KeyError(f"{origin}: lacks {missing[:3]}{'...' if len(missing) > 3 else ''}")
@@ -106,9 +117,11 @@ def copy_weights_into_engine(eng, sd: Dict[str, torch.Tensor], origin: str = "st
         src = sd[k].to(device=dst.device, dtype=dst.dtype)    # the trainer's parameter table keeps pointing at them
         if dst.shape != src.shape:
             raise ValueError(f"{origin}: {k} has shape {tuple(src.shape)}, engine expects {tuple(dst.shape)}")
-        if k.endswith("gate_proj.weight") or k.endswith("up_proj.weight"):
+        if llama and (k.endswith("gate_proj.weight") or k.endswith("up_proj.weight")):
             continue                                          # interleaved storage: handled below
         dst.copy_(src)
+    if not llama:
+        return
     d = eng.dims
     for i, L in enumerate(eng.layers):
         gate, up = sd[f"model.layers.{i}.mlp.gate_proj.weight"], sd[f"model.layers.{i}.mlp.up_proj.weight"]
@@ -151,7 +164,8 @@ def load_checkpoint(trainer, folder: str) -> int:
     trainer.flat_m.copy_(st["exp_avg"])
     trainer.flat_v.copy_(st["exp_avg_sq"])
     trainer.step_count = int(st["step"])
-    trainer.refresh_derived()
+    if hasattr(trainer, "refresh_derived"):                   # (the MPT trainer keeps no operand derived from the weights)
+        trainer.refresh_derived()
     trainer.zero_grad()
     return trainer.step_count
 

@@ -8,11 +8,15 @@ module therefore keeps the *interface* -- parameter names of the state dict (``t
 ``initialize_audio_tokenizer``, ``forward(input_ids, ..., labels, audio_encodings)`` -> ``CausalLMOutputWithPast``,
 ``prepare_inputs_for_generation`` and a greedy ``generate`` -- on plain ``torch.nn.Module`` containers; the arithmetic runs
 in ``HipMptEngine``; the training step lives in ``llark_amd.m2t.mpt_train_engine.HipMptTrainer`` (native loop, not wired
-into this wrapper's autograd).
+into this wrapper's autograd; ``llark_amd.m2t.train`` drives it for a model name that contains "mpt").  ``save_pretrained`` /
+``from_pretrained`` read and write a folder of ``config.json`` + ``pytorch_model.bin``, the format of the training checkpoints.
 """
 from __future__ import annotations
 
+import dataclasses
+import json
 import math
+import os
 from dataclasses import dataclass, field
 from typing import Any, Dict, Optional
 
@@ -47,7 +51,28 @@ class WrappedMPTConfig:
     tie_word_embeddings: bool = True
     use_mm_proj: bool = True
     mm_hidden_size: int = 512
+    tune_mm_mlp_adapter: bool = False
+    mm_use_audio_start_end: bool = False
     model_type: str = "wrapped_mpt_hip"
+
+    def to_dict(self) -> Dict[str, Any]:
+        return dataclasses.asdict(self)
+
+    def save_pretrained(self, folder: str) -> None:
+        """``config.json`` with this class's fields (what :meth:`from_pretrained` reads back)."""
+        os.makedirs(folder, exist_ok=True)
+        with open(os.path.join(folder, "config.json"), "w") as f:
+            json.dump(self.to_dict(), f, indent=2, sort_keys=True)
+
+    @classmethod
+    def from_pretrained(cls, folder: str, **overrides) -> "WrappedMPTConfig":
+        """The fields of ``<folder>/config.json`` this class knows (other keys of an MPT ``config.json`` are ignored), then ``overrides``."""
+        with open(os.path.join(folder, "config.json")) as f:
+            raw = json.load(f)
+        known = {f.name for f in dataclasses.fields(cls)}
+        kw = {k: v for k, v in raw.items() if k in known and k != "model_type"}
+        kw.update({k: v for k, v in overrides.items() if v is not None})
+        return cls(**kw)
 
     def validate(self) -> None:
         a = dict(ATTN_DEFAULTS, **self.attn_config)
@@ -118,6 +143,38 @@ class WrappedMPTForCausalLM(nn.Module):
         self._engine: Optional[HipMptEngine] = None
         self._engine_max = (8, 512)
         self._engine_precision = "split"
+
+    # ---- folders -------------------------------------------------------------------------------
+    WEIGHTS_NAME = "pytorch_model.bin"
+
+    def save_pretrained(self, folder: str) -> None:
+        """``config.json`` + ``pytorch_model.bin`` (a plain ``torch.save`` of the state dict under the reference's names)."""
+        self.config.vocab_size = self.transformer.wte.num_embeddings
+        self.config.save_pretrained(folder)
+        torch.save({k: v.detach().cpu() for k, v in self.state_dict().items()}, os.path.join(folder, self.WEIGHTS_NAME))
+
+    @classmethod
+    def from_pretrained(cls, folder: str, torch_dtype: Optional[torch.dtype] = None, mm_hidden_size: Optional[int] = None, **config_overrides):
+        """Opens a folder written by :meth:`save_pretrained` or by the training loop's ``save_checkpoint`` (m2t/train.py:62-68 passes
+        ``mm_hidden_size`` the same way).  Every tensor of the model must be in the file except ``mm_projector``, which a base model
+        does not have yet (``initialize_adapter_modules`` builds it); a key the model does not know is an error."""
+        cfg = WrappedMPTConfig.from_pretrained(folder, mm_hidden_size=mm_hidden_size, **config_overrides)
+        model = cls(cfg)
+        sd = torch.load(os.path.join(folder, cls.WEIGHTS_NAME), map_location="cpu")
+        own = model.state_dict()
+        for k in [k for k in sd if "mm_projector" in k and k in own and sd[k].shape != own[k].shape]:
+            del sd[k]                                         # a projector of another width (``mm_hidden_size`` given): built anew
+        unexpected = [k for k in sd if k not in own]
+        missing = [k for k in own if k not in sd and "mm_projector" not in k]
+        if unexpected or missing:
+            raise KeyError(f"{folder}: unexpected keys {unexpected[:3]}, missing keys {missing[:3]}")
+        rows = sd["transformer.wte.weight"].shape[0]
+        if rows != cfg.vocab_size:
+            model.resize_token_embeddings(rows)
+        model.load_state_dict(sd, strict=False)
+        if torch_dtype is not None:
+            model.to(torch_dtype)
+        return model
 
     # ---- reference surface ----------------------------------------------------------------------
     @property

@@ -115,6 +115,27 @@ class HipMptEngine:
         if "transformer.mm_projector.weight" in sd:
             self.proj_w, self.proj_b = self._bf16(sd["transformer.mm_projector.weight"]), self._f32(sd["transformer.mm_projector.bias"])
 
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """The weights under the reference's names (those of :meth:`load_state_dict`) as VIEWS of the engine's own tensors -- every MPT
+        tensor is stored as the reference lays it out (bf16 matrices, fp32 LayerNorm gains / biases), so writing into a value updates
+        the engine (checkpoint resume: llark_amd/m2t/checkpoint.py)."""
+        names = (("attn.Wqkv.weight", "wqkv"), ("attn.Wqkv.bias", "bqkv"), ("attn.out_proj.weight", "wo"), ("attn.out_proj.bias", "bo"),
+                 ("ffn.up_proj.weight", "wup"), ("ffn.up_proj.bias", "bup"), ("ffn.down_proj.weight", "wdown"), ("ffn.down_proj.bias", "bdown"),
+                 ("norm_1.weight", "n1w"), ("norm_1.bias", "n1b"), ("norm_2.weight", "n2w"), ("norm_2.bias", "n2b"),
+                 ("attn.q_ln.weight", "qlw"), ("attn.q_ln.bias", "qlb"), ("attn.k_ln.weight", "klw"), ("attn.k_ln.bias", "klb"))
+        sd = {"transformer.wte.weight": self.wte}
+        for i, B in enumerate(self.blocks):
+            for ref, nm in names:
+                t = getattr(B, nm)
+                if t is not None:
+                    sd[f"transformer.blocks.{i}.{ref}"] = t
+        sd["transformer.norm_f.weight"] = self.normf_w
+        if self.normf_b is not None:
+            sd["transformer.norm_f.bias"] = self.normf_b
+        if self.proj_w is not None:
+            sd["transformer.mm_projector.weight"], sd["transformer.mm_projector.bias"] = self.proj_w, self.proj_b
+        return sd
+
     # ---- buffers -------------------------------------------------------------------------------
     def _workspace(self, batch: int, s: int):
         if self._ws_key != (batch, s):

@@ -11,11 +11,13 @@ embeddings trainable and then freezes the OUTPUT embeddings, which is the same t
 the default keeps ``wte`` frozen; ``train_wte=True`` accumulates both of its uses (gather rows and the logits product).
 ``clip_qkv`` (clamp in the forward, gradient mask ``llark_clamp_bwd_bf16`` in the backward) and ``logit_scale`` (logits scaled in
 place before the loss, the factor folded into the scale of d(logits)) follow ``attn_config`` / ``config.logit_scale``.
+
+``forward_backward_packed`` (``--pack_sequences``): the ragged micro-batches of an optimizer step as ONE row stream on the ALiBi
+variable-length attention entry points (``llark_attn_*_varlen_alibi``), as in ``HipLlamaTrainer.forward_backward_packed``.
 """
 from __future__ import annotations
 
-import math
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -23,6 +25,19 @@ from .. import ops
 from .mpt_engine import HipMptEngine
 
 _BF = torch.bfloat16
+
+
+class _Packing:
+    """What a packed step (``forward_backward_packed``) changes in the body of ``forward_backward``: the rows are ONE stream (B = 1, S =
+    s_total) cut into sequences by ``seqs`` = [(off, len)] (device table ``table``); the head split runs on an identity rotation table of
+    s_total rows (the engine's own has ``smax``); the loss is normalised per group of rows (``groups`` = [(r0, r1)])."""
+
+    def __init__(self, plan, eng):
+        dev = eng.device
+        self.seqs, self.groups, self.max_len, self.s_total = list(plan.seqs), list(plan.groups), plan.max_len, plan.s_total
+        self.table = torch.tensor(self.seqs, dtype=torch.int32).to(dev)
+        self.cos = torch.ones((self.s_total, 64), dtype=torch.float32, device=dev)
+        self.sin = torch.zeros((self.s_total, 64), dtype=torch.float32, device=dev)
 
 
 class HipMptTrainer:
@@ -97,13 +112,42 @@ class HipMptTrainer:
         return hi[:, :width] if hi.shape[1] == width else hi[:, :width].contiguous()
 
     # ---------------------------------------------------------------------------------------------
-    def forward_backward(self, input_ids: torch.Tensor, audio_segments, labels: torch.Tensor, loss_scale: float = 1.0) -> torch.Tensor:
+    def forward_backward_packed(self, seqs=None, segs=(), labels=None, groups=None, loss_scale: Optional[float] = None, pad_id: int = 0,
+                                plan=None) -> torch.Tensor:
+        """A whole optimizer step of ragged sequences as ONE packed stream (see ``HipLlamaTrainer.forward_backward_packed``: same
+        arguments, same meaning of the loss -- each micro-batch's token mean, averaged over the micro-batches).  Attention runs on the
+        ALiBi variable-length kernels (llark_attn_*_varlen_alibi): the bias of a sequence is that of a ``batch = 1, s = len`` call, in the
+        forward and in the backward.  Each layer's saved K / V^T live in that layer's own cache memory viewed as one sequence of
+        s_total positions."""
+        from .data import pack_sequences
+
+        if plan is None:
+            plan = pack_sequences(seqs, labels, groups, segs, pad_id)
+        eng = self.eng
+        if plan.s_total > eng.max_batch * eng.smax:
+            raise ValueError(f"forward_backward_packed: s_total = {plan.s_total} packed rows do not fit the engine's caches "
+                             f"(max_batch * smax = {eng.max_batch} * {eng.smax} positions)")
+        return self.forward_backward(plan.ids.view(1, -1).to(eng.device), plan.segments, plan.labels.view(1, -1),
+                                     1.0 / len(plan.groups) if loss_scale is None else loss_scale, _packing=_Packing(plan, eng))
+
+    def forward_backward(self, input_ids: torch.Tensor, audio_segments, labels: torch.Tensor, loss_scale: float = 1.0,
+                         _packing: Optional[_Packing] = None) -> torch.Tensor:
         eng, d, dev = self.eng, self.eng.dims, self.eng.device
         B, S = input_ids.shape
+        pk = _packing                                                   # a packed step (forward_backward_packed): B = 1, S = s_total
         rows, D, E, nh = B * S, d.d_model, d.expansion_ratio * d.d_model, d.n_heads
         V = d.vocab_size
         f32, bf = dict(dtype=torch.float32, device=dev), dict(dtype=_BF, device=dev)
-        eng.reset(B)
+        eng.reset(B if pk is None else eng.max_batch)
+        if pk is None:
+            smax = eng.smax
+            caches = lambda i: (eng.k_cache[i], eng.vt_cache[i])
+            cos, sin = eng.cos, eng.sin
+        else:
+            # the caches are scratch during training: a layer's saved K / V^T are ONE sequence of S positions at the head of its own memory
+            smax = S
+            caches = lambda i: (eng.k_cache[i].view(-1)[: nh * S * 128].view(1, nh, S, 128), eng.vt_cache[i].view(-1)[: nh * S * 128].view(1, nh, 128, S))
+            cos, sin = pk.cos, pk.sin                                   # identity tables of S rows: eng.cos has only eng.smax
         ids_flat = input_ids.reshape(-1).contiguous()
         h = torch.empty((rows, D), **f32)
         ops.embed_gather(ids_flat, eng.wte, h)
@@ -111,7 +155,7 @@ class HipMptTrainer:
         for (b, start, frames) in audio_segments:
             F = frames.shape[0]
             a16, _ = ops.split16(frames.contiguous(), _BF, want_lo=False, kmult=64)
-            r0 = b * S + start + 1
+            r0 = (b * S if pk is None else pk.seqs[b][0]) + start + 1
             ops.gemm16(a16, None, eng.proj_w, eng.proj_b, D, ops.EPI_F32, c=h[r0: r0 + F])
             seg_rows.append(torch.arange(r0, r0 + F, device=dev))
             seg_a16.append(a16[:, : d.mm_hidden_size])
@@ -131,11 +175,14 @@ class HipMptTrainer:
                 ops.layernorm_f32_(qkv[:, :D], Bk.qlw, Bk.qlb, d.ln_eps)
                 ops.layernorm_f32_(qkv[:, D: 2 * D], Bk.klw, Bk.klb, d.ln_eps)
             q = torch.empty((B, nh, S, 128), **bf)
-            kc, vc = eng.k_cache[i], eng.vt_cache[i]
-            ops.rope_split_heads(qkv, B, S, nh, 128, 0, eng.cos, eng.sin, q, kc, vc)
+            kc, vc = caches(i)
+            ops.rope_split_heads(qkv, B, S, nh, 128, 0, cos, sin, q, kc, vc)
             att = torch.empty((rows, D), **bf)
             lse = torch.empty((B * nh, S), **f32)                         # per-query log-sum-exp: the backward recomputes P from it
-            ops.attn_prefill_lse(q, kc, vc, B, S, nh, 128, att, lse, alibi_slopes=eng.slopes)
+            if pk is None:
+                ops.attn_prefill_lse(q, kc, vc, B, S, nh, 128, att, lse, alibi_slopes=eng.slopes)
+            else:
+                ops.attn_prefill_lse_varlen(q, kc, vc, pk.table, pk.seqs, pk.max_len, S, nh, 128, att, lse, alibi_slopes=eng.slopes)
             ops.gemm16(att, None, Bk.wo, Bk.bo, D, ops.EPI_RESID, c=h, resid=h)
             st.update(x1=x1, q=q, att=att, lse=lse, h_mid=h.clone())
             x2 = torch.empty((rows, D), **bf)
@@ -156,7 +203,16 @@ class HipMptTrainer:
         if d.logit_scale is not None:                    # modeling_mpt.py:410-416: logits *= logit_scale; d(raw logits) = scale * d(logits)
             lscale = float(d.logit_scale)
             ops.scale_f32_(logits, lscale)
-        loss = ops.cross_entropy_fwd_bwd(logits.view(B, S, V), labels.to(dev), dlogits, loss_scale * lscale)
+        if pk is not None:
+            # per micro-batch: the mean over ITS shifted targets.  Every sequence's first label is -100, so no row predicts across a
+            # boundary; a group's last row is the last position of its (1, rows) call and does not count either.
+            lab, loss = labels.reshape(-1).to(dev), None
+            for (r0, r1) in pk.groups:
+                li = ops.cross_entropy_fwd_bwd(logits[r0:r1].view(1, r1 - r0, V), lab[r0:r1].view(1, r1 - r0), dlogits[r0:r1], loss_scale * lscale)
+                loss = li if loss is None else loss + li
+            loss = loss / len(pk.groups)
+        else:
+            loss = ops.cross_entropy_fwd_bwd(logits.view(B, S, V), labels.to(dev), dlogits, loss_scale * lscale)
         del logits
         # ---------------- backward ----------------
         g = self.grads
@@ -167,7 +223,7 @@ class HipMptTrainer:
         dh = torch.empty((rows, D), **f32)
         ops.layernorm_bwd(h, eng.normf_w, dtmp, d.ln_eps, dh, g["normf_w"], g.get("normf_b"), False)
         del dlogits
-        Sp, BH, scale, smax = ops.round_up(S, 64), B * nh, 1.0 / math.sqrt(128.0), eng.smax
+        BH = B * nh
         for i in reversed(range(len(eng.blocks))):
             Bk, st, pre = eng.blocks[i], saved[i], f"blocks.{i}."
             # ---- MLP ----
@@ -197,16 +253,20 @@ class HipMptTrainer:
             dO = torch.empty((BH, S, 128), **bf)
             ops.split_heads16(dctx16, B, S, nh, 128, dO)
             q = st["q"].view(BH, S, 128)
-            kc, vtc = eng.k_cache[i], eng.vt_cache[i]
+            kc, vtc = caches(i)
             # flash-style backward (csrc/attn_bwd.hip), ALiBi inside: P is recomputed per tile from the forward's log-sum-exp
             v_rm = torch.empty((BH, S, 128), **bf)
             ops.transpose16(vtc, smax, 128, S, v_rm, 128, BH, 128 * smax, S * 128)
             dq, dk, dv = (torch.empty((BH, S, 128), **f32) for _ in range(3))
             dsum = torch.empty((BH, S), **f32)
-            ops.attn_backward(q, kc, v_rm, dO, st["att"], st["lse"], dsum, B, S, nh, 128, dq, dk, dv,
-                              alibi_slopes=eng.slopes)
+            if pk is None:
+                ops.attn_backward(q, kc, v_rm, dO, st["att"], st["lse"], dsum, B, S, nh, 128, dq, dk, dv,
+                                  alibi_slopes=eng.slopes)
+            else:
+                ops.attn_backward_varlen(q, kc, v_rm, dO, st["att"], st["lse"], dsum, pk.table, pk.seqs, pk.max_len, S, nh, 128, dq, dk, dv,
+                                         alibi_slopes=eng.slopes)
             dqkv = torch.empty((rows, 3 * D), **bf)
-            ops.rope_merge_bwd(dq, dk, dv, eng.cos, eng.sin, B, S, nh, 128, 0, dqkv)      # identity rotation: heads -> [rows][3D]
+            ops.rope_merge_bwd(dq, dk, dv, cos, sin, B, S, nh, 128, 0, dqkv)      # identity rotation: heads -> [rows][3D]
             if d.qk_ln:                                    # through the LayerNorms over q and k (fp32), then back to bf16
                 d32 = dqkv.float()
                 dpre = torch.empty((rows, 2 * D), **f32)

@@ -1595,29 +1595,42 @@ def _seq_table(seqs: torch.Tensor, seqs_host, max_len: int, s_total: int) -> int
 
 
 def attn_prefill_lse_varlen(q, k_cache, vt_cache, seqs: torch.Tensor, seqs_host, max_len: int, s_total: int, nh: int, hd: int,
-                            out: torch.Tensor, lse: torch.Tensor) -> None:
+                            out: torch.Tensor, lse: torch.Tensor, alibi_slopes: Optional[torch.Tensor] = None) -> None:
     """:func:`attn_prefill_lse` over the sequences of a table: the layouts of a ``batch = 1, s = s_total`` call, ``seqs`` int32 [nseq][2] =
-    (off, len) on the device, ``seqs_host`` the host list it was built from (checked here: :func:`check_seq_table`)."""
+    (off, len) on the device, ``seqs_host`` the host list it was built from (checked here: :func:`check_seq_table`).  ``alibi_slopes``
+    fp32 [nh] (MPT) selects the ALiBi entry point: the bias of a sequence is that of the uniform call with ``batch = 1, s = len``."""
     table = _seq_table(seqs, seqs_host, max_len, s_total)
     smax = k_cache.shape[-2]
     bf = torch.bfloat16
-    with _timed("attn_prefill_lse_varlen", 0.0):
-        check(_lib.lib().llark_attn_prefill_bf16_lse_varlen(_dev(q, "q", bf), _dev(k_cache, "k_cache", bf), _dev(vt_cache, "vt_cache", bf), table,
-                                                            len(seqs_host), max_len, s_total, nh, hd, smax, _dev(out, "out", bf),
-                                                            _dev(lse, "lse", torch.float32), _stream()), "attn_prefill_lse_varlen")
+    args = (_dev(q, "q", bf), _dev(k_cache, "k_cache", bf), _dev(vt_cache, "vt_cache", bf), table, len(seqs_host), max_len, s_total, nh, hd,
+            smax, _dev(out, "out", bf), _dev(lse, "lse", torch.float32))
+    if alibi_slopes is None:
+        with _timed("attn_prefill_lse_varlen", 0.0):
+            check(_lib.lib().llark_attn_prefill_bf16_lse_varlen(*args, _stream()), "attn_prefill_lse_varlen")
+    else:
+        assert alibi_slopes.numel() == nh
+        with _timed("attn_prefill_lse_varlen_alibi", 0.0):
+            check(_lib.lib().llark_attn_prefill_bf16_lse_varlen_alibi(*args, _dev(alibi_slopes, "alibi_slopes", torch.float32), _stream()),
+                  "attn_prefill_lse_varlen_alibi")
 
 
 def attn_backward_varlen(q, k_cache, v_rm, dO, o, lse, dsum, seqs: torch.Tensor, seqs_host, max_len: int, s_total: int, nh: int, hd: int,
-                         dq: torch.Tensor, dk: torch.Tensor, dv: torch.Tensor) -> None:
-    """:func:`attn_backward` over the sequences of a table (see :func:`attn_prefill_lse_varlen`)."""
+                         dq: torch.Tensor, dk: torch.Tensor, dv: torch.Tensor, alibi_slopes: Optional[torch.Tensor] = None) -> None:
+    """:func:`attn_backward` over the sequences of a table (see :func:`attn_prefill_lse_varlen`); ``alibi_slopes`` as given to the forward."""
     table = _seq_table(seqs, seqs_host, max_len, s_total)
     smax = k_cache.shape[-2]
     bf, f32 = torch.bfloat16, torch.float32
-    with _timed("attn_backward_varlen", 0.0):
-        check(_lib.lib().llark_attn_backward_bf16_varlen(_dev(q, "q", bf), _dev(k_cache, "k_cache", bf), _dev(v_rm, "v_rm", bf), _dev(dO, "dO", bf),
-                                                         _dev(o, "o", bf), _dev(lse, "lse", f32), _dev(dsum, "dsum", f32), table, len(seqs_host),
-                                                         max_len, s_total, nh, hd, smax, _dev(dq, "dq", f32), _dev(dk, "dk", f32),
-                                                         _dev(dv, "dv", f32), _stream()), "attn_backward_varlen")
+    args = (_dev(q, "q", bf), _dev(k_cache, "k_cache", bf), _dev(v_rm, "v_rm", bf), _dev(dO, "dO", bf), _dev(o, "o", bf), _dev(lse, "lse", f32),
+            _dev(dsum, "dsum", f32), table, len(seqs_host), max_len, s_total, nh, hd, smax, _dev(dq, "dq", f32), _dev(dk, "dk", f32),
+            _dev(dv, "dv", f32))
+    if alibi_slopes is None:
+        with _timed("attn_backward_varlen", 0.0):
+            check(_lib.lib().llark_attn_backward_bf16_varlen(*args, _stream()), "attn_backward_varlen")
+    else:
+        assert alibi_slopes.numel() == nh
+        with _timed("attn_backward_varlen_alibi", 0.0):
+            check(_lib.lib().llark_attn_backward_bf16_varlen_alibi(*args, _dev(alibi_slopes, "alibi_slopes", f32), _stream()),
+                  "attn_backward_varlen_alibi")
 
 
 def attn_backward_fused_varlen(q, k_cache, v_rm, dO: torch.Tensor, o, lse, dsum, seqs: torch.Tensor, seqs_host, max_len: int, s_total: int,
