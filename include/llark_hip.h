@@ -555,6 +555,22 @@ int llark_attn_decode_rope_bf16_rows(const float* qkv, int batch, int nh, int hd
                                      int smax, void* out, void* out_lo, const float* alibi_slopes, llark_stream_t stream);
 int llark_decode_advance_rows(const float* logits, int ldl, int vocab, int batch, const int64_t* choice, int* pos_rows, int* state,
                               int64_t* next_ids, int64_t* out_col, int ld_out, int64_t eos, int64_t pad, llark_stream_t stream);
+/* MPT ragged decode step, the whole attention front in one launch (m2t/llava/model/mpt/attention.py: qkv.clamp_ -> q_ln / k_ln ->
+ * head split -> attention with the ALiBi bias; replaces llark_clamp_f32 + 2 x llark_layernorm_f32 + llark_attn_decode_rope_bf16_rows
+ * with identity tables).  qkv fp32 [batch][ldq], laid out q | k | v with nh*128 columns each, is READ ONLY.  Workgroup (h, b) reads
+ * p = pos_rows[b]; p < 0 or p >= smax: idle slot, nothing is written to its caches and its output head is zero.  Otherwise, for its own
+ * 128 columns of q, k and v: (1) clamp to +-clip_qkv (clip_qkv <= 0: no clamp; v too; a NaN is kept); (2) when q_ln_w != NULL the
+ * LayerNorm of q_ln / k_ln over the WHOLE nh*128-wide clamped q row, respectively k row (fp32 statistics, two-pass mean / variance,
+ * recomputed per workgroup; q_ln_w and k_ln_w come together, q_ln_b / k_ln_b are nullable on their own); (3) rounding to the bf16
+ * plane(s) as llark_rope_split_heads does (lo planes: all or none); (4) k appended at row p of slot b's K cache, v at column p of its
+ * V^T cache; (5) attention over keys 0 .. p with alibi_slopes[h] * (j - p) added to the scaled scores.  Caches k [batch][nh][smax][128],
+ * v^T [batch][nh][128][smax]; out bf16 [batch][nh * 128]; dynamic LDS holds smax scores.  hd == 128, smax % 8 == 0, nh*128 <= 8192,
+ * alibi_slopes != NULL, ldq >= 3*nh*128, ldq % 4 == 0, qkv 16-byte aligned; anything else: LLARK_ERR_UNSUPPORTED / LLARK_ERR_INVALID
+ * before any launch.  No atomics, no waiting between workgroups. */
+int llark_mpt_attn_decode_rows(const float* qkv, int ldq, int batch, int nh, int hd, const int* pos_rows, float clip_qkv,
+                               const float* q_ln_w, const float* q_ln_b, const float* k_ln_w, const float* k_ln_b, float ln_eps,
+                               void* k_cache, void* vt_cache, void* k_cache_lo, void* vt_cache_lo, int smax, void* out, void* out_lo,
+                               const float* alibi_slopes, llark_stream_t stream);
 /* Shared prompt prefix in the ragged slot mode (csrc/attn_shared.hip).  Under the contract of infer_from_webdataset.py every
  * (question, answer) pair of a sample is its own example and all of them start with the same audio block: the slots of one clip hold
  * the same K/V at their first positions.

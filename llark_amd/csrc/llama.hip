@@ -644,71 +644,20 @@ static void launch_attn_prefill(hipStream_t st, const bf16_t* q, const bf16_t* k
 // Decode attention (one new token per sequence): one block per (batch, head).
 //   q [B][nh][1][128] bf16, caches as above, `total` keys visible. fp32 math, HBM-bound on the cache.
 // ------------------------------------------------------------------------------------------
-// UBT = loads in flight per lane and pass.  16 waves x 4 keys x UBT cover 256 (UBT = 4) or 512 (UBT = 8) keys per round of the K pass, 8 threads
-// x 8 keys x UBT the same per round of the V pass: with the 25 s prompt (371 + up to 64 keys) UBT = 8 walks each pass in ONE round of memory
-// latency instead of two (round 6).  UBT = 4 at 16 waves is capped at 72 registers so that the workgroup fits a CU next to a chained o_proj
-// workgroup (llark_attn_decode_rope_bf16_chain: 4 x 72 + 2 x 104 of 512 registers per SIMD lane).
-// ROWS: `pos_dev` is pos_rows[batch], one position per sequence (llark_attn_decode_rope_bf16_rows: ragged decode over batch slots);
-// a slot whose position is < 0 (idle) or >= smax writes nothing to the caches and zeros to its output head.
-template <int NW, int UBT, bool ROWS = false>
-__global__ __launch_bounds__(NW * 64, (NW >= 16 && UBT == 4) ? 7 : 1) void attn_decode_kernel(const bf16_t* __restrict__ q, bf16_t* kc, bf16_t* vtc,
-                                                              const bf16_t* __restrict__ q_lo, bf16_t* kc_lo, bf16_t* vtc_lo,
-                                                              bf16_t* __restrict__ out, bf16_t* __restrict__ out_lo,
-                                                              int nh, int total, int smax, float scale,
-                                                              const int* __restrict__ pos_dev, const float* __restrict__ alibi,
-                                                              const float* __restrict__ qkv, const float* __restrict__ cos_t,
-                                                              const float* __restrict__ sin_t, unsigned* chain_done) {
-    // NW waves per (batch, head).  A single sequence has only nh blocks (32 of 256 CUs busy): there the block is 16 waves
-    // wide so that the whole K pass and the whole V pass are each ONE round of loads in flight (the kernel is a chain of
-    // memory latencies, not bandwidth); batched decode keeps 4 waves per block.
+// The K pass, the softmax and the V pass of one (batch, head) workgroup, shared by every decode-attention kernel: `sq` (LDS) holds the
+// query, `sp` (dynamic LDS) takes the scores, `red` (LDS, 2 * NW floats) the block reductions.  Begins with the barrier that makes the
+// caller's q (LDS) and its own cache append (global) visible to the whole block.
+template <int NW, int UBT>
+__device__ __forceinline__ void attn_decode_body(const float* sq, float* sp, float* red, const bf16_t* kc, const bf16_t* vtc,
+                                                 const bf16_t* kc_lo, const bf16_t* vtc_lo, bf16_t* __restrict__ out,
+                                                 bf16_t* __restrict__ out_lo, int nh, int total, int smax, float scale,
+                                                 const float* __restrict__ alibi) {
     constexpr int NT = NW * 64;
     constexpr int UB = UBT;                       // loads in flight per lane
     constexpr int PARTS = NT / 128;               // threads sharing one output dim in the PV pass
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if constexpr (ROWS) {
-        const int p = pos_dev[blockIdx.y];                       // uniform per block: the whole block leaves together
-        if (p < 0 || p >= smax) {
-            if (threadIdx.x < 128)
-                store_split(out, out_lo, (size_t)blockIdx.y * (nh * 128) + blockIdx.x * 128 + threadIdx.x, 0.0f);
-            return;
-        }
-        total = p + 1;
-    } else if (pos_dev) total = *pos_dev + 1;     // graph-captured decode: keys 0..pos are visible
-    float* sp = (float*)smem;                    // [total] scores / probabilities
-    __shared__ float sq[128];
-    __shared__ float red[2 * NW];
     const int h = blockIdx.x, b = blockIdx.y;
     const size_t bh = (size_t)b * nh + h;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (qkv) {
-        // Fused RoPE + cache write of the new token (decode): this block owns (batch b, head h), so it rotates its own q / k,
-        // appends k and v to the caches with exactly the arithmetic and rounding of rope_split_kernel, keeps q in LDS (the
-        // bf16 q planes are never materialised) and only then -- after the barrier that makes its own global writes visible
-        // to the whole block -- walks the cache including the row it just wrote.  Saves one launch per layer and token.
-        const int pos = total - 1, H = nh * 128;
-        const float* row = qkv + (size_t)b * 3 * H + h * 128;
-        const bool split = kc_lo != nullptr;
-        if (tid < 64) {
-            const int d = tid;
-            const float c = cos_t[(size_t)pos * 64 + d], sn = sin_t[(size_t)pos * 64 + d];
-            const float q1 = row[d], q2 = row[d + 64], k1 = row[H + d], k2 = row[H + d + 64];
-            const float qa = __fadd_rn(__fmul_rn(q1, c), __fmul_rn(-q2, sn));
-            const float qb = __fadd_rn(__fmul_rn(q2, c), __fmul_rn(q1, sn));
-            const float ka = __fadd_rn(__fmul_rn(k1, c), __fmul_rn(-k2, sn));
-            const float kb2 = __fadd_rn(__fmul_rn(k2, c), __fmul_rn(k1, sn));
-            const bf16_t ha = (bf16_t)qa, hb = (bf16_t)qb;
-            sq[d] = (float)ha + (split ? (float)(bf16_t)(qa - (float)ha) : 0.0f);
-            sq[d + 64] = (float)hb + (split ? (float)(bf16_t)(qb - (float)hb) : 0.0f);
-            const size_t ko = (bh * (size_t)smax + pos) * 128;
-            store_split(kc, kc_lo, ko + d, ka);
-            store_split(kc, kc_lo, ko + d + 64, kb2);
-        } else if (tid >= 128 && tid < 256) {
-            const int d = tid - 128;
-            store_split(vtc, vtc_lo, (bh * 128 + d) * (size_t)smax + pos, row[2 * H + d]);
-        }
-    } else if (tid < 128) {
-        sq[tid] = (float)q[bh * 128 + tid] + (q_lo ? (float)q_lo[bh * 128 + tid] : 0.0f);
-    }
     __syncthreads();
     // ---- scores: 16 lanes per key (16 B each = one 256-B cache row per 16-lane group, 1 KiB per wave instruction),
     //      4 keys per wave and iteration; the 16 partial dot products meet in a shuffle tree
@@ -813,7 +762,148 @@ __global__ __launch_bounds__(NW * 64, (NW >= 16 && UBT == 4) ? 7 : 1) void attn_
 #pragma unroll
     for (int o = 1; o < PARTS; o <<= 1) acc += __shfl_xor(acc, o, 64);
     if (part == 0) store_split(out, out_lo, (size_t)b * (nh * 128) + h * 128 + d, acc * inv);
+}
+
+// UBT = loads in flight per lane and pass.  16 waves x 4 keys x UBT cover 256 (UBT = 4) or 512 (UBT = 8) keys per round of the K pass, 8 threads
+// x 8 keys x UBT the same per round of the V pass: with the 25 s prompt (371 + up to 64 keys) UBT = 8 walks each pass in ONE round of memory
+// latency instead of two (round 6).  UBT = 4 at 16 waves is capped at 72 registers so that the workgroup fits a CU next to a chained o_proj
+// workgroup (llark_attn_decode_rope_bf16_chain: 4 x 72 + 2 x 104 of 512 registers per SIMD lane).
+// ROWS: `pos_dev` is pos_rows[batch], one position per sequence (llark_attn_decode_rope_bf16_rows: ragged decode over batch slots);
+// a slot whose position is < 0 (idle) or >= smax writes nothing to the caches and zeros to its output head.
+template <int NW, int UBT, bool ROWS = false>
+__global__ __launch_bounds__(NW * 64, (NW >= 16 && UBT == 4) ? 7 : 1) void attn_decode_kernel(const bf16_t* __restrict__ q, bf16_t* kc, bf16_t* vtc,
+                                                              const bf16_t* __restrict__ q_lo, bf16_t* kc_lo, bf16_t* vtc_lo,
+                                                              bf16_t* __restrict__ out, bf16_t* __restrict__ out_lo,
+                                                              int nh, int total, int smax, float scale,
+                                                              const int* __restrict__ pos_dev, const float* __restrict__ alibi,
+                                                              const float* __restrict__ qkv, const float* __restrict__ cos_t,
+                                                              const float* __restrict__ sin_t, unsigned* chain_done) {
+    // NW waves per (batch, head).  A single sequence has only nh blocks (32 of 256 CUs busy): there the block is 16 waves
+    // wide so that the whole K pass and the whole V pass are each ONE round of loads in flight (the kernel is a chain of
+    // memory latencies, not bandwidth); batched decode keeps 4 waves per block.
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if constexpr (ROWS) {
+        const int p = pos_dev[blockIdx.y];                       // uniform per block: the whole block leaves together
+        if (p < 0 || p >= smax) {
+            if (threadIdx.x < 128)
+                store_split(out, out_lo, (size_t)blockIdx.y * (nh * 128) + blockIdx.x * 128 + threadIdx.x, 0.0f);
+            return;
+        }
+        total = p + 1;
+    } else if (pos_dev) total = *pos_dev + 1;     // graph-captured decode: keys 0..pos are visible
+    float* sp = (float*)smem;                    // [total] scores / probabilities
+    __shared__ float sq[128];
+    __shared__ float red[2 * NW];
+    const int h = blockIdx.x, b = blockIdx.y;
+    const size_t bh = (size_t)b * nh + h;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (qkv) {
+        // Fused RoPE + cache write of the new token (decode): this block owns (batch b, head h), so it rotates its own q / k,
+        // appends k and v to the caches with exactly the arithmetic and rounding of rope_split_kernel, keeps q in LDS (the
+        // bf16 q planes are never materialised) and only then -- after the barrier that makes its own global writes visible
+        // to the whole block -- walks the cache including the row it just wrote.  Saves one launch per layer and token.
+        const int pos = total - 1, H = nh * 128;
+        const float* row = qkv + (size_t)b * 3 * H + h * 128;
+        const bool split = kc_lo != nullptr;
+        if (tid < 64) {
+            const int d = tid;
+            const float c = cos_t[(size_t)pos * 64 + d], sn = sin_t[(size_t)pos * 64 + d];
+            const float q1 = row[d], q2 = row[d + 64], k1 = row[H + d], k2 = row[H + d + 64];
+            const float qa = __fadd_rn(__fmul_rn(q1, c), __fmul_rn(-q2, sn));
+            const float qb = __fadd_rn(__fmul_rn(q2, c), __fmul_rn(q1, sn));
+            const float ka = __fadd_rn(__fmul_rn(k1, c), __fmul_rn(-k2, sn));
+            const float kb2 = __fadd_rn(__fmul_rn(k2, c), __fmul_rn(k1, sn));
+            const bf16_t ha = (bf16_t)qa, hb = (bf16_t)qb;
+            sq[d] = (float)ha + (split ? (float)(bf16_t)(qa - (float)ha) : 0.0f);
+            sq[d + 64] = (float)hb + (split ? (float)(bf16_t)(qb - (float)hb) : 0.0f);
+            const size_t ko = (bh * (size_t)smax + pos) * 128;
+            store_split(kc, kc_lo, ko + d, ka);
+            store_split(kc, kc_lo, ko + d + 64, kb2);
+        } else if (tid >= 128 && tid < 256) {
+            const int d = tid - 128;
+            store_split(vtc, vtc_lo, (bh * 128 + d) * (size_t)smax + pos, row[2 * H + d]);
+        }
+    } else if (tid < 128) {
+        sq[tid] = (float)q[bh * 128 + tid] + (q_lo ? (float)q_lo[bh * 128 + tid] : 0.0f);
+    }
+    attn_decode_body<NW, UBT>(sq, sp, red, kc, vtc, kc_lo, vtc_lo, out, out_lo, nh, total, smax, scale, alibi);
     chain_signal(ChainSync{nullptr, 0u, chain_done});                 // round 6: a chained consumer (o_proj) may be waiting for this head
+}
+
+// MPT decode front (m2t/llava/model/mpt/attention.py: qkv.clamp_ -> q_ln / k_ln -> head split) fused into the ragged decode attention:
+// workgroup (head h, slot b) clamps its own 128 columns of q, k and v, applies the LayerNorm of q_ln / k_ln -- whose statistics run over
+// the WHOLE nh*128-wide clamped row, recomputed here by wave 0 (q) and wave 1 (k) with the lane layout, the two-pass form and the reduction
+// order of mpt_layernorm_kernel (one wave per row) -- rounds to the bf16 plane(s) as rope_split_kernel does, appends k and v to the slot's
+// caches, keeps q (hi + lo) in LDS and runs attn_decode_body.  `qkv` is only read.  Idle slots as in attn_decode_kernel<.., ROWS>.
+__device__ __forceinline__ float clamp_keep_nan(float v, float lim) {            // clamp_f32_kernel; lim <= 0: no clamp
+    return (lim > 0.0f && v == v) ? fminf(fmaxf(v, -lim), lim) : v;
+}
+
+template <int NW, int UBT>
+__global__ __launch_bounds__(NW * 64, (NW >= 16 && UBT == 4) ? 7 : 1) void mpt_attn_decode_kernel(
+    const float* __restrict__ qkv, int ldq, int nh, const int* __restrict__ pos_rows, float clip, const float* __restrict__ q_ln_w,
+    const float* __restrict__ q_ln_b, const float* __restrict__ k_ln_w, const float* __restrict__ k_ln_b, float eps, bf16_t* kc, bf16_t* vtc,
+    bf16_t* kc_lo, bf16_t* vtc_lo, int smax, bf16_t* __restrict__ out, bf16_t* __restrict__ out_lo, float scale,
+    const float* __restrict__ alibi) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int pos = pos_rows[blockIdx.y];                        // uniform per block: the whole block leaves together
+    if (pos < 0 || pos >= smax) {
+        if (threadIdx.x < 128) store_split(out, out_lo, (size_t)blockIdx.y * (nh * 128) + blockIdx.x * 128 + threadIdx.x, 0.0f);
+        return;
+    }
+    float* sp = (float*)smem;
+    __shared__ float sq[128];
+    __shared__ float red[2 * NW];
+    __shared__ float stat[4];                                    // mean, rstd of the q row; mean, rstd of the k row
+    const int h = blockIdx.x, b = blockIdx.y, H = nh * 128;
+    const size_t bh = (size_t)b * nh + h;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const float* row = qkv + (size_t)b * ldq;
+    const bool ln = q_ln_w != nullptr, split = kc_lo != nullptr;
+    // this thread's own element, requested before the statistics: threads 0..127 q, 128..255 k; v needs none and is appended at once
+    const int d = tid & 127, isk = tid >> 7;
+    float x = 0.0f, g = 1.0f, be = 0.0f;
+    if (tid < 256) {
+        x = clamp_keep_nan(row[isk * H + h * 128 + d], clip);
+        if (ln) {
+            g = (isk ? k_ln_w : q_ln_w)[h * 128 + d];
+            const float* bp = isk ? k_ln_b : q_ln_b;
+            be = bp ? bp[h * 128 + d] : 0.0f;
+        }
+    }
+    if (tid >= 128 && tid < 256)
+        store_split(vtc, vtc_lo, (bh * 128 + d) * (size_t)smax + pos, clamp_keep_nan(row[2 * H + h * 128 + d], clip));
+    if (ln) {
+        if (wv < 2) {
+            const float4* xr = (const float4*)(row + wv * H);
+            const int w4 = H >> 2;
+            float s = 0.0f;
+            for (int c = lane; c < w4; c += 64) {
+                float4 v = xr[c];
+                v.x = clamp_keep_nan(v.x, clip), v.y = clamp_keep_nan(v.y, clip), v.z = clamp_keep_nan(v.z, clip), v.w = clamp_keep_nan(v.w, clip);
+                s += (v.x + v.y) + (v.z + v.w);
+            }
+            const float mean = wave_sum(s) / (float)H;
+            float q = 0.0f;
+            for (int c = lane; c < w4; c += 64) {                 // second pass: the row comes back from L2
+                float4 v = xr[c];
+                v.x = clamp_keep_nan(v.x, clip), v.y = clamp_keep_nan(v.y, clip), v.z = clamp_keep_nan(v.z, clip), v.w = clamp_keep_nan(v.w, clip);
+                const float a = v.x - mean, bb = v.y - mean, cc = v.z - mean, dd = v.w - mean;
+                q += (a * a + bb * bb) + (cc * cc + dd * dd);
+            }
+            const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)H + eps);
+            if (lane == 0) stat[2 * wv] = mean, stat[2 * wv + 1] = rstd;
+        }
+        __syncthreads();
+        if (tid < 256) x = (x - stat[2 * isk]) * stat[2 * isk + 1] * g + be;
+    }
+    if (tid < 128) {
+        const bf16_t hi = (bf16_t)x;
+        sq[d] = (float)hi + (split ? (float)(bf16_t)(x - (float)hi) : 0.0f);
+    } else if (tid < 256) {
+        store_split(kc, kc_lo, (bh * (size_t)smax + pos) * 128 + d, x);
+    }
+    attn_decode_body<NW, UBT>(sq, sp, red, kc, vtc, kc_lo, vtc_lo, out, out_lo, nh, pos + 1, smax, scale, alibi);
 }
 
 // Every decode-attention launch goes through attn_decode(): the entry points at the end of this file fill in what they were given (the
@@ -1233,6 +1323,52 @@ extern "C" int llark_attn_decode_rope_bf16_rows(const float* qkv, int batch, int
                                              vt_cache_lo, smax, out, out_lo, alibi_slopes, stream);
     a.from = POS_ROWS, a.pos_rows = pos_rows;
     return attn_decode(a);
+}
+
+// MPT ragged decode step: clip_qkv clamp + qk_ln + head split + cache append + ALiBi decode attention in one launch (contract: llark_hip.h).
+extern "C" int llark_mpt_attn_decode_rows(const float* qkv, int ldq, int batch, int nh, int hd, const int* pos_rows, float clip_qkv,
+                                          const float* q_ln_w, const float* q_ln_b, const float* k_ln_w, const float* k_ln_b, float ln_eps,
+                                          void* k_cache, void* vt_cache, void* k_cache_lo, void* vt_cache_lo, int smax, void* out,
+                                          void* out_lo, const float* alibi_slopes, llark_stream_t stream) {
+    LLARK_REQUIRE(qkv && pos_rows && k_cache && vt_cache && out, "mpt_attn_decode_rows: null pointer (qkv, pos_rows, k_cache, vt_cache, out)");
+    LLARK_REQUIRE(alibi_slopes, "mpt_attn_decode_rows: alibi_slopes is null");
+    if (hd != 128) {
+        set_error("mpt_attn_decode_rows: hd must be 128, got %d", hd);
+        return LLARK_ERR_UNSUPPORTED;
+    }
+    LLARK_REQUIRE((k_cache_lo == nullptr) == (vt_cache_lo == nullptr) && (k_cache_lo == nullptr) == (out_lo == nullptr),
+                  "mpt_attn_decode_rows: give all lo planes (k_cache_lo, vt_cache_lo, out_lo) or none");
+    LLARK_REQUIRE((q_ln_w == nullptr) == (k_ln_w == nullptr) && (q_ln_w || (!q_ln_b && !k_ln_b)),
+                  "mpt_attn_decode_rows: q_ln_w and k_ln_w come together, and a bias needs them");
+    LLARK_REQUIRE(batch > 0 && nh > 0, "mpt_attn_decode_rows: bad shape batch=%d nh=%d", batch, nh);
+    if ((long)nh * 128 > 8192) {
+        set_error("mpt_attn_decode_rows: nh*128 = %ld is wider than the LayerNorm limit 8192", (long)nh * 128);
+        return LLARK_ERR_UNSUPPORTED;
+    }
+    LLARK_REQUIRE(smax > 0 && smax % 8 == 0, "mpt_attn_decode_rows: smax must be a positive multiple of 8, got %d", smax);
+    LLARK_REQUIRE(ldq >= 3 * nh * 128 && ldq % 4 == 0 && ((uintptr_t)qkv & 15) == 0,
+                  "mpt_attn_decode_rows: ldq must be >= 3*nh*128 and a multiple of 4, qkv 16-byte aligned (ldq=%d nh=%d)", ldq, nh);
+    const size_t lds = (size_t)smax * sizeof(float);
+    if (lds > 128 * 1024) {
+        set_error("mpt_attn_decode_rows: smax %d too long for the LDS score buffer", smax);
+        return LLARK_ERR_UNSUPPORTED;
+    }
+    const float scale = (float)(1.0 / sqrt((double)hd));
+    auto launch = [&](auto kern, int threads) {
+        kern<<<dim3(nh, batch), threads, lds, (hipStream_t)stream>>>(qkv, ldq, nh, pos_rows, clip_qkv, q_ln_w, q_ln_b, k_ln_w, k_ln_b, ln_eps,
+                                                                     (bf16_t*)k_cache, (bf16_t*)vt_cache, (bf16_t*)k_cache_lo, (bf16_t*)vt_cache_lo,
+                                                                     smax, (bf16_t*)out, (bf16_t*)out_lo, scale, alibi_slopes);
+    };
+    static PerDeviceOnce once;
+    const bool first = once.first();
+    if (lds > 48 * 1024 && (first || (int)lds > once.slot())) {
+        (void)hipFuncSetAttribute((const void*)mpt_attn_decode_kernel<4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute((const void*)mpt_attn_decode_kernel<16, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        once.slot() = (int)lds;
+    }
+    if ((long)nh * batch < 256) launch(mpt_attn_decode_kernel<16, 4>, 1024);          // as attn_decode(): 16 waves below 256 workgroups
+    else launch(mpt_attn_decode_kernel<4, 8>, 256);
+    return check_launch("mpt_attn_decode_rows");
 }
 
 extern "C" int llark_decode_advance_rows(const float* logits, int ldl, int vocab, int batch, const int64_t* choice, int* pos_rows, int* state,

@@ -220,13 +220,16 @@ class InflightScheduler:
 
 
 class EngineSlots:
-    """:class:`InflightScheduler` backend on the HIP engine's ragged slot mode (``HipLlamaEngine.init_slots`` /
-    ``prefill_slots`` / ``decode_slots`` / ``release_slots``) of a ``WrappedLlamav2ForCausalLM``."""
+    """:class:`InflightScheduler` backend on the HIP engine's ragged slot mode (``init_slots`` / ``prefill_slots`` / ``decode_slots`` /
+    ``release_slots`` of ``HipLlamaEngine`` or ``HipMptEngine``) of a ``WrappedLlamav2ForCausalLM`` or ``WrappedMPTForCausalLM``.  The
+    MPT wrapper splices audio by its patch tokens (``audio_patch_branch``) and its engine has no shared-prefix form (``init_slots``
+    raises ``NotImplementedError``)."""
 
     def __init__(self, model, n_slots: int, share_prefix: bool = False):
         from .llamav2 import plan_audio_splice
 
         self._plan = plan_audio_splice
+        self._plan_kw = dict(patch_branch=True) if getattr(model, "audio_patch_branch", False) else {}
         self.model = model
         self.eng = model.engine
         if share_prefix:
@@ -248,7 +251,7 @@ class EngineSlots:
         for i, (p, enc) in enumerate(zip(prompts, encodings)):
             if enc is not None:
                 feats = torch.as_tensor(enc).to(device=eng.device, dtype=torch.float32)
-                segs += [(i, start, f) for (_, start, f) in self._plan(p[None], [feats], cfg, False)]
+                segs += [(i, start, f) for (_, start, f) in self._plan(p[None], [feats], cfg, False, **self._plan_kw)]
         if past is None:
             logits = eng.prefill_slots([p.to(eng.device) for p in prompts], segs, slots)
         else:
@@ -483,16 +486,28 @@ def main(argv=None):
     return recs
 
 
+def _load_tokenizer(args):
+    """The tokenizer of either backbone, loaded as llark_amd/m2t/train.py:main does."""
+    from transformers import AutoTokenizer
+
+    return AutoTokenizer.from_pretrained(args.model_name_or_path, model_max_length=args.model_max_length, padding_side="right", use_fast=False)
+
+
 def _load_for_inference(args, max_batch: int):
     """Tokenizer + model of ``args.model_name_or_path`` set up for generation (audio tokens, engine) -> (model, tokenizer, end_seq,
     multimodal config)."""
-    from transformers import AutoTokenizer
-
-    from .llamav2 import WrappedLlamav2ForCausalLM
     from .special_tokens import DEFAULT_AUDIO_END_TOKEN, DEFAULT_AUDIO_PATCH_TOKEN, DEFAULT_AUDIO_START_TOKEN
+    from .train import backbone_of
 
-    tok = AutoTokenizer.from_pretrained(args.model_name_or_path, model_max_length=args.model_max_length, padding_side="right", use_fast=False)
-    model = WrappedLlamav2ForCausalLM.from_pretrained(args.model_name_or_path, torch_dtype=torch.bfloat16)
+    tok = _load_tokenizer(args)
+    if backbone_of(args.model_name_or_path) == "mpt":          # the reference's rule (m2t/train.py:62), as in this project's train.main
+        from .mpt import WrappedMPTForCausalLM
+
+        model = WrappedMPTForCausalLM.from_pretrained(args.model_name_or_path, torch_dtype=torch.bfloat16, mm_hidden_size=args.mm_hidden_size)
+    else:
+        from .llamav2 import WrappedLlamav2ForCausalLM
+
+        model = WrappedLlamav2ForCausalLM.from_pretrained(args.model_name_or_path, torch_dtype=torch.bfloat16)
     if args.mm_hidden_size:
         model.config.mm_hidden_size = args.mm_hidden_size
     if tok.pad_token is None:                                           # m2t/train.py:110-124 adds it at training time
@@ -544,6 +559,10 @@ def main_shards(argv=None):
     args = ap.parse_args(argv)
     if not 1 <= args.slots <= 64:
         ap.error(f"--slots must be in 1 .. 64, got {args.slots}")
+    from .train import backbone_of
+
+    if args.share_prefix and backbone_of(args.model_name_or_path) == "mpt":
+        ap.error("--share-prefix is not available for an MPT model: the shared-prefix decode attention takes no ALiBi bias")
     model, tok, end_seq, mm_cfg = _load_for_inference(args, args.slots)
     recs = infer_from_shards(model, tok, args.eval_data_path, mm_cfg, end_seq, outfile=args.outfile, slots=args.slots,
                              max_samples=args.max_samples, max_new_tokens=args.max_new_tokens, prompt=args.prompt, seed=args.seed,

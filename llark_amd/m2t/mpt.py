@@ -129,6 +129,8 @@ class WrappedMPTModel(nn.Module):
 
 
 class WrappedMPTForCausalLM(nn.Module):
+    audio_patch_branch = True                  # plan_audio_splice(..., patch_branch=True): m2t/models/mpt.py splices by the patch tokens
+
     def __init__(self, config: WrappedMPTConfig):
         super().__init__()
         config.validate()
@@ -290,8 +292,14 @@ class WrappedMPTForCausalLM(nn.Module):
                 "use_cache": kwargs.get("use_cache", True), "audio_encodings": kwargs.get("audio_encodings", None)}
 
     @torch.no_grad()
-    def generate(self, input_ids=None, audio_encodings=None, max_new_tokens: int = 20, stopping_criteria=None, eos_token_id=None, **kwargs):
-        """Greedy loop driven by :meth:`prepare_inputs_for_generation` (prompt with audio once, then one token per step)."""
+    def generate(self, input_ids=None, audio_encodings=None, max_new_tokens: int = 20, stopping_criteria=None, eos_token_id=None,
+                 attention_mask=None, pad_token_id=None, **kwargs):
+        """Greedy loop driven by :meth:`prepare_inputs_for_generation` (prompt with audio once, then one token per step).  An
+        ``attention_mask`` with zeros (left- or right-padded) runs every row as if it were alone on the engine's ragged slot mode
+        (:meth:`_generate_ragged`); ``None`` or all ones takes this uniform path and never enters the slot mode."""
+        if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
+            return self._generate_ragged(input_ids, attention_mask, audio_encodings, max_new_tokens, stopping_criteria, eos_token_id,
+                                         pad_token_id)
         ids = input_ids.to(self.engine.device)
         past = None
         for _ in range(max_new_tokens):
@@ -306,3 +314,47 @@ class WrappedMPTForCausalLM(nn.Module):
             if stopping_criteria is not None and any(bool(c(ids, scores)) for c in stopping_criteria):
                 break
         return ids
+
+    def _generate_ragged(self, input_ids, attention_mask, audio_encodings, max_new_tokens, stopping_criteria, eos_token_id, pad_token_id):
+        """generate() over a padded batch (``WrappedLlamav2ForCausalLM._generate_ragged``): row b is the sequence
+        input_ids[b][mask[b]] at positions 0 .. len_b - 1, one engine slot per row (prefill_slots / decode_slots).  Returns the HF
+        layout: the input as given followed by the new tokens; a row that emitted EOS continues with the pad token (EOS when none)."""
+        eng = self.engine
+        B, S = input_ids.shape
+        am = attention_mask.to(device="cpu", dtype=torch.bool)
+        if am.shape != (B, S):
+            raise ValueError(f"attention_mask shape {tuple(am.shape)} does not match input_ids {(B, S)}")
+        lens = am.sum(1)
+        if bool((lens == 0).any()):
+            raise ValueError("attention_mask selects no token in some row")
+        ids_dev = input_ids.to(eng.device)
+        if max_new_tokens <= 0:
+            return ids_dev
+        ids_cpu = input_ids.detach().cpu()
+        rows = [ids_cpu[b][am[b]] for b in range(B)]
+        packed = torch.zeros((B, int(lens.max())), dtype=torch.int64)               # left-aligned copy for the splice plan
+        for b, r in enumerate(rows):
+            packed[b, : r.numel()] = r
+        segs = []
+        if audio_encodings is not None and self.config.use_mm_proj:
+            feats = audio_encodings
+            feats = [f.to(eng.device, torch.float32) for f in feats] if isinstance(feats, (list, tuple)) else feats.to(eng.device, torch.float32)
+            segs = plan_audio_splice(packed, feats, self.transformer.audio_encoder_config, False, patch_branch=True)
+        use_eos = eos_token_id is not None and eos_token_id >= 0
+        eos_k, pad_k = (int(eos_token_id), int(eos_token_id if pad_token_id is None else pad_token_id)) if use_eos else (-1, 0)
+        out = torch.empty((B, S + max_new_tokens), dtype=torch.int64, device=eng.device)
+        out[:, :S] = ids_dev
+        eng.init_slots(B)
+        scores = eng.prefill_slots([r.to(eng.device) for r in rows], segs, range(B))
+        nxt, _ = eng.advance_slots(scores, eos_k, pad_k, out[:, S], advance=False)
+        n = 1
+        while True:
+            if use_eos and all(st != ops.ROW_ACTIVE for st in eng.slot_state_host):
+                break
+            if stopping_criteria is not None and any(bool(c(out[:, : S + n], scores)) for c in stopping_criteria):
+                break
+            if n == max_new_tokens:
+                break
+            nxt, _, scores = eng.decode_slots(nxt, eos_k, pad_k, out[:, S + n])
+            n += 1
+        return out[:, : S + n]

@@ -992,6 +992,31 @@ def attn_decode_rope_rows(qkv: torch.Tensor, batch: int, nh: int, hd: int, pos_r
                                                           _opt(alibi_slopes, "alibi_slopes", torch.float32), _stream()), "attn_decode_rope_rows")
 
 
+def mpt_attn_decode_rows(qkv: torch.Tensor, batch: int, nh: int, hd: int, pos_rows: torch.Tensor, clip_qkv, q_ln_w, q_ln_b, k_ln_w, k_ln_b,
+                         ln_eps: float, k_cache, vt_cache, out, k_cache_lo=None, vt_cache_lo=None, out_lo=None, alibi_slopes=None) -> None:
+    """MPT ragged decode front + attention in one launch: clamp (``clip_qkv`` None / 0: none), qk_ln (``q_ln_w`` None: none), head split,
+    cache append at ``pos_rows`` (int32 [batch] on the device, < 0 = idle slot) and ALiBi decode attention.  ``qkv`` fp32
+    [batch][>= 3*nh*hd] (row stride = its leading dimension) is only read."""
+    smax = k_cache.shape[-2]
+    bf = torch.bfloat16
+    assert qkv.dim() == 2 and qkv.shape[0] == batch and qkv.stride(1) == 1 and pos_rows.numel() == batch and out.numel() == batch * nh * hd
+    assert k_cache.shape == (batch, nh, smax, hd) and vt_cache.shape == (batch, nh, hd, smax)
+    assert out_lo is None or out_lo.shape == out.shape
+    for c in (k_cache_lo, vt_cache_lo):
+        assert c is None or c.shape in (k_cache.shape, vt_cache.shape)
+    for t in (q_ln_w, q_ln_b, k_ln_w, k_ln_b, alibi_slopes):
+        assert t is None or t.numel() >= (nh if t is alibi_slopes else nh * hd)
+    with _timed("mpt_attn_decode_rows", 0.0):
+        check(_lib.lib().llark_mpt_attn_decode_rows(_dev(qkv, "qkv", torch.float32, contiguous=False), qkv.stride(0), batch, nh, hd,
+                                                    _dev(pos_rows, "pos_rows", torch.int32), float(clip_qkv or 0.0),
+                                                    _opt(q_ln_w, "q_ln_w", torch.float32), _opt(q_ln_b, "q_ln_b", torch.float32),
+                                                    _opt(k_ln_w, "k_ln_w", torch.float32), _opt(k_ln_b, "k_ln_b", torch.float32), float(ln_eps),
+                                                    _dev(k_cache, "k_cache", bf), _dev(vt_cache, "vt_cache", bf),
+                                                    _opt(k_cache_lo, "k_cache_lo", bf), _opt(vt_cache_lo, "vt_cache_lo", bf), smax,
+                                                    _dev(out, "out", bf), _opt(out_lo, "out_lo", bf),
+                                                    _opt(alibi_slopes, "alibi_slopes", torch.float32), _stream()), "mpt_attn_decode_rows")
+
+
 SHARED_GROUP_MEMBERS = 16                  # members per group of attn_decode_rope_shared (csrc/attn_shared.hip: GK_MEMBERS)
 SHARED_GROUP_STRIDE = 3 + SHARED_GROUP_MEMBERS          # int32 per group: source slot, shared length, members, member slots
 SHARED_STATUS = {1: "shared length is not a positive multiple of 8 (or exceeds smax)", 2: "a group must have 1 .. 16 members",
