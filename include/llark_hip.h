@@ -555,6 +555,38 @@ int llark_attn_decode_rope_bf16_rows(const float* qkv, int batch, int nh, int hd
                                      int smax, void* out, void* out_lo, const float* alibi_slopes, llark_stream_t stream);
 int llark_decode_advance_rows(const float* logits, int ldl, int vocab, int batch, const int64_t* choice, int* pos_rows, int* state,
                               int64_t* next_ids, int64_t* out_col, int ld_out, int64_t eos, int64_t pad, llark_stream_t stream);
+/* Token sampling on the device (csrc/sample.hip): the producer of llark_decode_advance_rows' `choice`.
+ *   llark_sample_rows: one workgroup per row r of logits fp32 [rows][ldl] (columns >= vocab are never read).  slot = slot_of_row[r]
+ *     (int32 [rows], NULL: slot = r; rows map to DISTINCT slots); a row whose slot is outside [0, slots) or, when state != NULL (int32
+ *     [slots] of LLARK_ROW_*), not LLARK_ROW_ACTIVE is skipped: nothing of it is read or written.  Otherwise, in fp32 and in the
+ *     processor order of HF 4.29.2:
+ *       1. repetition penalty (1 = off): a token t whose bit (t & 31) of word seen[slot][t >> 5] is set: l < 0 ? l * penalty : l / penalty
+ *          (seen uint32 [slots][ld_seen], ld_seen >= ceil(vocab / 32));
+ *       do_sample == 0: choice[r] = first maximal index of the penalised row (a NaN counts as the maximum), its seen bit is set (seen
+ *          != NULL), nothing else is written;
+ *       2. l / temperature;  3. top_k (0 = off, else clamped to 1 .. vocab): keep l >= the k-th largest value, ties at the threshold
+ *          all kept;  4. top_p (1 = off): with e_i = exp(l_i - max) over the kept set and Z their sum, keep token i iff the sum of
+ *          the e_j with l_j > l_i is < top_p * Z -- tokens with equal logits stay or go together, so tokens exactly tied at the
+ *          boundary are all kept;  5. the token is the smallest index whose inclusive cumulative kept mass, in token order, exceeds
+ *          x * Z_kept.  x = u[r] (u fp32 [rows] in [0, 1)) when u != NULL, else (w >> 8) * 2^-24 with w the first word of
+ *          Philox4x32-10 under key (seed lo32, seed hi32) and counter (draws[slot], 0, stream_id[slot] lo32, hi32); stream_id int64
+ *          [slots], NULL: the slot index.
+ *       Then choice[r] = token (always in [0, vocab)), its seen bit is set (seen != NULL), draws[slot] += 1 (draws != NULL), kept[r] =
+ *       size of the final kept set and thresh[r] = its smallest post-temperature logit (both nullable).  A row that holds a NaN, whose
+ *       maximum is +-inf or whose kept mass is not a positive finite number takes the greedy token of the penalised row instead, gets
+ *       kept[r] = 0, and adds 1 to *fallbacks (nullable).  Sums have a fixed order: results are bit-reproducible.
+ *     LLARK_ERR_INVALID before any launch: a null logits / choice, rows, slots or vocab <= 0, ldl < vocab, rows > slots without
+ *     slot_of_row, repetition_penalty <= 0, a penalty != 1 without seen, ld_seen too small, and when sampling temperature <= 0, top_p
+ *     outside (0, 1], top_k < 0, u and draws both NULL.  LLARK_ERR_UNSUPPORTED: vocab > 65536.
+ *   llark_seen_mark_rows: sets, in seen[slot_of_row[r]] (NULL: slot r), the bits of ids[offs[r] .. offs[r] + lens[r]) for r < rows (ids
+ *     int64 [n_ids]; offs, lens int32 [rows]).  Ids outside [0, vocab), rows with a slot outside [0, slots) or a range outside [0, n_ids)
+ *     are ignored.  Clearing a slot is a memset of its row by the caller. */
+int llark_sample_rows(const float* logits, int ldl, int vocab, int rows, int slots, const int* state, const int* slot_of_row,
+                      unsigned* seen, int ld_seen, int do_sample, float temperature, int top_k, float top_p, float repetition_penalty,
+                      const float* u, long long seed, int* draws, const int64_t* stream_id, int64_t* choice, int* kept, float* thresh,
+                      int* fallbacks, llark_stream_t stream);
+int llark_seen_mark_rows(const int64_t* ids, long long n_ids, const int* offs, const int* lens, const int* slot_of_row, int rows,
+                         int slots, int vocab, unsigned* seen, int ld_seen, llark_stream_t stream);
 /* MPT ragged decode step, the whole attention front in one launch (m2t/llava/model/mpt/attention.py: qkv.clamp_ -> q_ln / k_ln ->
  * head split -> attention with the ALiBi bias; replaces llark_clamp_f32 + 2 x llark_layernorm_f32 + llark_attn_decode_rope_bf16_rows
  * with identity tables).  qkv fp32 [batch][ldq], laid out q | k | v with nh*128 columns each, is READ ONLY.  Workgroup (h, b) reads

@@ -105,15 +105,20 @@ class InflightScheduler:
     ``audio_token_ids``), the backend copies those positions (``fork(src, dsts, n)``) and prefills only the rest
     (``prefill(slots, suffixes, [None, ...], past=[n, ...])``); the trace gains ``("fork", src, dst, n)``.  The examples that need a full
     prefill go first, in one call as ever; a backend without ``fork`` gets nothing but full prefills.  Off (the default), calls and
-    trace are exactly what they were."""
+    trace are exactly what they were.
+
+    ``sampling``: the backend draws its tokens (:class:`llark_amd.m2t.sampling.DeviceSampler`) and every ``prefill`` call also gets
+    ``indices=`` (the examples' input indices: their random streams) and ``whole=`` (their full prompts -- what a forked slot has seen
+    although only its suffix is prefilled).  Off (the default), the backend's signature is what it was."""
 
     def __init__(self, backend, n_slots: int, max_new_tokens: int = 512, eos: Optional[int] = None, stop_fn=None,
-                 share_prefix: bool = False, min_shared: int = MIN_SHARED):
+                 share_prefix: bool = False, min_shared: int = MIN_SHARED, sampling: bool = False):
         if n_slots < 1:
             raise ValueError(f"n_slots must be >= 1, got {n_slots}")
         self.backend, self.n_slots, self.max_new_tokens = backend, n_slots, max_new_tokens
         self.share_prefix = bool(share_prefix) and hasattr(backend, "fork")
         self.min_shared = min_shared
+        self.sampling = bool(sampling)
         self.eos = eos if eos is not None and eos >= 0 else None
         self.stop_fn = stop_fn                    # (prompt ids, generated ids) -> bool: keyword stop; may keep state per row
         self.trace: List[Tuple] = []
@@ -156,9 +161,13 @@ class InflightScheduler:
         forks = self._plan_forks(table, new) if self.share_prefix else {}
         full = [b for b in new if b not in forks]
         toks: Dict[int, int] = {}
+
+        def extra(slots):
+            return dict(indices=[table[b]["index"] for b in slots], whole=[table[b]["prompt"] for b in slots]) if self.sampling else {}
         if full:
             self.trace.append(("prefill", tuple(full), tuple(table[b]["index"] for b in full)))
-            toks.update(zip(full, self.backend.prefill(full, [table[b]["prompt"] for b in full], [table[b]["enc"] for b in full])))
+            toks.update(zip(full, self.backend.prefill(full, [table[b]["prompt"] for b in full], [table[b]["enc"] for b in full],
+                                                       **extra(full))))
         if forks:
             calls: Dict[Tuple[int, int], List[int]] = {}
             for b in sorted(forks):
@@ -170,7 +179,7 @@ class InflightScheduler:
             forked = sorted(forks)
             self.trace.append(("prefill", tuple(forked), tuple(table[b]["index"] for b in forked)))
             firsts = self.backend.prefill(forked, [table[b]["prompt"][forks[b][1]:] for b in forked], [None] * len(forked),
-                                          past=[forks[b][1] for b in forked])
+                                          past=[forks[b][1] for b in forked], **extra(forked))
             toks.update(zip(forked, firsts))
         return toks
 
@@ -223,9 +232,10 @@ class EngineSlots:
     """:class:`InflightScheduler` backend on the HIP engine's ragged slot mode (``init_slots`` / ``prefill_slots`` / ``decode_slots`` /
     ``release_slots`` of ``HipLlamaEngine`` or ``HipMptEngine``) of a ``WrappedLlamav2ForCausalLM`` or ``WrappedMPTForCausalLM``.  The
     MPT wrapper splices audio by its patch tokens (``audio_patch_branch``) and its engine has no shared-prefix form (``init_slots``
-    raises ``NotImplementedError``)."""
+    raises ``NotImplementedError``).  ``sampling`` (a :class:`llark_amd.m2t.sampling.SamplingParams`): tokens come from the device
+    sampler, whose stream id is the example's input index."""
 
-    def __init__(self, model, n_slots: int, share_prefix: bool = False):
+    def __init__(self, model, n_slots: int, share_prefix: bool = False, sampling=None):
         from .llamav2 import plan_audio_splice
 
         self._plan = plan_audio_splice
@@ -237,6 +247,8 @@ class EngineSlots:
         else:
             self.eng.init_slots(n_slots)
         self.ids = torch.zeros((n_slots,), dtype=torch.int64, device=self.eng.device)
+        self.sampling = sampling if sampling is not None and sampling.active else None
+        self.sampler = None                                       # built at the first prefill, which tells the logits' width
         cfg = model.get_model().audio_encoder_config
         self.audio_token_ids = tuple(int(t) for t in (getattr(cfg, name, None) for name in ("audio_start_token", "audio_end_token", "audio_patch_token"))
                                      if t is not None)
@@ -244,7 +256,7 @@ class EngineSlots:
     def fork(self, src, dsts, n):
         self.eng.fork_slots(src, dsts, n)
 
-    def prefill(self, slots, prompts, encodings, past=None):
+    def prefill(self, slots, prompts, encodings, past=None, indices=None, whole=None):
         eng = self.eng
         cfg = self.model.get_model().audio_encoder_config
         segs = []
@@ -256,34 +268,56 @@ class EngineSlots:
             logits = eng.prefill_slots([p.to(eng.device) for p in prompts], segs, slots)
         else:
             logits = eng.prefill_slots([p.to(eng.device) for p in prompts], segs, slots, past=past)
-        first = logits.argmax(-1)                                  # what generate() picks after the prompt
+        if self.sampling is not None:
+            if self.sampler is None:
+                from .sampling import DeviceSampler
+
+                self.sampler = DeviceSampler(self.sampling, eng.n_slots, logits.shape[-1], eng.device)
+            self.sampler.admit(slots, prompts if whole is None else whole, slots if indices is None else indices)
+            first = self.sampler(logits, state=eng.slot_state, slot_of_row=list(slots))
+        else:
+            first = logits.argmax(-1)                              # what generate() picks after the prompt
         self.ids[torch.tensor(slots, dtype=torch.long, device=eng.device)] = first
         return first.cpu().tolist()
 
     def decode(self):
-        self.ids, host, _ = self.eng.decode_slots(self.ids)
+        if self.sampler is not None:
+            self.ids, host, _ = self.eng.decode_slots(self.ids, sample=self._sample)
+        else:
+            self.ids, host, _ = self.eng.decode_slots(self.ids)
         return host.tolist()
+
+    def _sample(self, logits):
+        return self.sampler(logits, state=self.eng.slot_state)
 
     def release(self, slots):
         self.eng.release_slots(slots)
+        if self.sampler is not None:
+            self.sampler.release(slots)
 
 
 @torch.no_grad()
 def generate_inflight(model, examples: Iterable[Sequence[Any]], slots: int = 8, max_new_tokens: int = 512,
                       keywords: Sequence[str] = ("###",), tokenizer=None, trace: Optional[list] = None,
-                      share_prefix: bool = False) -> Iterator[Tuple[int, torch.Tensor]]:
-    """Greedy generation with in-flight slot refill.  ``examples`` yields ``(prompt_ids, encoding[, max_new_tokens[, prefix_key]])`` with prompts
+                      share_prefix: bool = False, sampling=None) -> Iterator[Tuple[int, torch.Tensor]]:
+    """Generation (greedy unless ``sampling``) with in-flight slot refill.  ``examples`` yields ``(prompt_ids, encoding[, max_new_tokens[, prefix_key]])`` with prompts
     of any length; up to ``slots`` of them decode together, each at its own KV-cache length, and a finished row's slot is refilled
     from the iterable (contiguous free slots prefilled as one batch) while the others keep decoding.  Stops per row as in
     :func:`generate_batch` (keyword -- needs ``tokenizer`` --, EOS or budget).  Yields ``(index, prompt + continuation ids)`` as
     examples complete.  ``model`` may provide ``slot_backend(n_slots)`` (any :class:`InflightScheduler` backend); otherwise its
     engine's ragged slot mode serves it.  ``trace``: a list that receives the scheduler's events.  ``share_prefix``: examples with
     equal ``prefix_key`` (the questions of one clip) share the K/V of their common leading tokens -- prefilled once, copied to the
-    siblings' slots, and read once per group by the decode step (:class:`InflightScheduler`, ``HipLlamaEngine.fork_slots``)."""
+    siblings' slots, and read once per group by the decode step (:class:`InflightScheduler`, ``HipLlamaEngine.fork_slots``).
+    ``sampling``: a :class:`llark_amd.m2t.sampling.SamplingParams`; tokens are then chosen by the device sampler with the example's
+    index as its random stream, so a completion depends neither on the slot the example landed in nor on ``slots`` (a model's own
+    ``slot_backend`` is greedy: sampling with one is refused)."""
     if keywords and tokenizer is None:
         raise ValueError("generate_inflight: keyword stopping needs the tokenizer")
     make = getattr(model, "slot_backend", None)
-    backend = make(slots) if make is not None else EngineSlots(model, slots, share_prefix)
+    sampling = sampling if sampling is not None and sampling.active else None
+    if sampling is not None and make is not None:
+        raise ValueError("generate_inflight: sampling needs the engine's own slot backend; this model provides slot_backend()")
+    backend = make(slots) if make is not None else EngineSlots(model, slots, share_prefix, sampling)
     eos = getattr(getattr(model, "generation_config", None), "eos_token_id", None)
     stop_fn = None
     if keywords:
@@ -291,7 +325,7 @@ def generate_inflight(model, examples: Iterable[Sequence[Any]], slots: int = 8, 
             if row["stop"] is None:
                 row["stop"] = KeywordsStoppingCriteria(keywords=list(keywords), tokenizer=tokenizer, input_ids=row["prompt"][None])
             return bool(row["stop"](torch.cat((row["prompt"], gen))[None], None))
-    sched = InflightScheduler(backend, slots, max_new_tokens, eos, stop_fn, share_prefix=share_prefix)
+    sched = InflightScheduler(backend, slots, max_new_tokens, eos, stop_fn, share_prefix=share_prefix, sampling=sampling is not None)
     if trace is not None:
         sched.trace = trace
     yield from sched.run(examples)
@@ -405,14 +439,15 @@ SHARD_COLUMNS = ["example_id", "prompt_text", "original_completion_text", "model
 def infer_from_shards(model, tokenizer, shards: str, multimodal_cfg: Dict[str, Any], end_seq: Sequence[int], outfile: Optional[str] = None,
                       slots: int = 8, max_samples: Optional[int] = None, max_new_tokens: int = 512, prompt: Optional[str] = None,
                       seed: int = 0, allow_pickle: bool = False, header: str = DEFAULT_CONVERSATION_HEADER,
-                      share_prefix: bool = False) -> List[Dict[str, str]]:
+                      share_prefix: bool = False, sampling=None) -> List[Dict[str, str]]:
     """Local tar shards -> CSV under the contract of ``scripts/inference/infer_from_webdataset.py:51-151``: every (question,
     answer) pair of a sample is one example whose prompt is its own human turn up to "### Assistant:" (audio placeholder first
     or last by a draw seeded with ``seed``); ``prompt`` overrides every question (the reference's ``--prompt``: audio first).
     Records ``example_id`` (the sample's tar key, repeated across its questions), ``prompt_text``, ``original_completion_text``
     (the pair's answer) and ``model_completion_text``, in input order.  ``max_samples`` caps the number of examples.  All
     generation runs through :func:`generate_inflight` with ``slots`` batch slots.  ``share_prefix``: the questions of one sample
-    (its tar key is their ``prefix_key``) share the K/V of their common leading tokens when the audio placeholder comes first."""
+    (its tar key is their ``prefix_key``) share the K/V of their common leading tokens when the audio placeholder comes first.
+    ``sampling``: a :class:`llark_amd.m2t.sampling.SamplingParams` (its ``seed`` is the draws'; ``seed`` here shuffles the questions)."""
     from .data import element_to_conversations, expand_urls, iter_tar_samples
 
     rng = random.Random(seed)
@@ -436,7 +471,7 @@ def infer_from_shards(model, tokenizer, shards: str, multimodal_cfg: Dict[str, A
                 yield ids, enc, None, conv["id"]
 
     outs: Dict[int, torch.Tensor] = dict(generate_inflight(model, examples(), slots=slots, max_new_tokens=max_new_tokens, tokenizer=tokenizer,
-                                                           share_prefix=share_prefix))
+                                                           share_prefix=share_prefix, sampling=sampling))
     records = []
     for i, m in enumerate(meta):
         records.append(dict(m, model_completion_text=tokenizer.decode(extract_response_tokens(outs[i], end_seq))))
@@ -534,7 +569,7 @@ def main_shards(argv=None):
     """``shards`` mode, with the flags of the reference's ``scripts/inference/infer_from_webdataset.py:154-190`` (+ ``--slots``):
     python -m llark_amd.m2t.infer_driver shards --model_name_or_path <dir> --eval_data_path "shards-{000000..000021}.tar" \
         --outfile results/infer.csv [--prompt "Describe ..."] [--max-samples N] [--max_new_tokens 2048] [--slots 8] [--allow-pickle]
-        [--share-prefix]
+        [--share-prefix] [--do-sample --temperature 0.8 --top-k 50 --top-p 0.9 --sample-seed 0] [--repetition-penalty 1.3]
     ``--allow-pickle``: read ``.pyd`` (pickled) encodings -- unpickling runs code, pass it only for shards you trust."""
     import argparse
 
@@ -551,12 +586,27 @@ def main_shards(argv=None):
     ap.add_argument("--allow-pickle", action="store_true")
     ap.add_argument("--share-prefix", action="store_true", help="the questions of one sample share the K/V of their common leading "
                     "tokens (audio placeholder first): prefilled once, read once per group in the decode step")
+    ap.add_argument("--do-sample", action="store_true", help="draw the tokens on the device instead of taking the greedy one "
+                    "(scripts/inference/infer_from_webdataset.py:102-103 keeps do_sample / temperature commented out)")
+    ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--top-k", type=int, default=0, help="0: off")
+    ap.add_argument("--top-p", type=float, default=1.0, help="1: off")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0, help="1: off; applies to greedy decoding too")
+    ap.add_argument("--sample-seed", type=int, default=0, help="seed of the draws (--seed is the question shuffle's); a completion "
+                    "depends on it and on the example's index, not on --slots")
     ap.add_argument("--mm_hidden_size", type=int, default=None)
     ap.add_argument("--model_max_length", type=int, default=2048)
     ap.add_argument("--llm-precision", default="split", choices=["split", "bf16"])
     for ignored in ("--ckpt-num", "--report_to", "--bf16", "--tf32", "--output_dir"):
         ap.add_argument(ignored, default=None, help="accepted for script compatibility")
     args = ap.parse_args(argv)
+    from .sampling import SamplingParams
+
+    try:
+        sampling = SamplingParams(do_sample=args.do_sample, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
+                                  repetition_penalty=args.repetition_penalty, seed=args.sample_seed)
+    except ValueError as e:
+        ap.error(str(e))
     if not 1 <= args.slots <= 64:
         ap.error(f"--slots must be in 1 .. 64, got {args.slots}")
     from .train import backbone_of
@@ -566,7 +616,7 @@ def main_shards(argv=None):
     model, tok, end_seq, mm_cfg = _load_for_inference(args, args.slots)
     recs = infer_from_shards(model, tok, args.eval_data_path, mm_cfg, end_seq, outfile=args.outfile, slots=args.slots,
                              max_samples=args.max_samples, max_new_tokens=args.max_new_tokens, prompt=args.prompt, seed=args.seed,
-                             allow_pickle=args.allow_pickle, share_prefix=args.share_prefix)
+                             allow_pickle=args.allow_pickle, share_prefix=args.share_prefix, sampling=sampling if sampling.active else None)
     print(f"writing {len(recs)} results to {args.outfile}")
     return recs
 

@@ -26,6 +26,7 @@ from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutpu
 from .. import ops
 from . import AudioEncoderConfig
 from .engine import HipLlamaEngine, LlamaDims
+from .sampling import DeviceSampler, params_from_generate
 from .special_tokens import DEFAULT_AUDIO_END_TOKEN, DEFAULT_AUDIO_PATCH_TOKEN, DEFAULT_AUDIO_START_TOKEN
 
 
@@ -372,17 +373,25 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
 
     @torch.no_grad()
     def generate(self, input_ids=None, audio_encodings=None, max_new_tokens: int = 20, do_sample: bool = False,
-                 stopping_criteria=None, eos_token_id=None, temperature: float = 1.0, attention_mask=None, **kwargs):
+                 stopping_criteria=None, eos_token_id=None, temperature: float = 1.0, attention_mask=None, top_k: Optional[int] = None,
+                 top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, seed: Optional[int] = None, **kwargs):
         """Greedy / temperature sampling loop with the semantics of HF 4.29.2 ``generate`` driven by
         :meth:`prepare_inputs_for_generation`: the full prompt (with audio) once, then one token per step
         against the engine's KV cache; ``stopping_criteria`` are called as ``c(ids, scores)`` each step
         (m2t/generate.py:31-44, m2t/infer.py:146-152).  An ``attention_mask`` with zeros (left-padded, the HF convention for
         batched decoder-only generation, or right-padded) runs every row as if it were alone on the engine's ragged slot mode
-        (:meth:`_generate_ragged`); ``None`` or all ones takes this uniform path."""
+        (:meth:`_generate_ragged`); ``None`` or all ones takes this uniform path.
+
+        ``do_sample`` with ``temperature`` alone draws with ``torch.multinomial`` from torch's global generator, as ever.  Any of
+        ``top_k`` / ``top_p`` / ``repetition_penalty`` / ``seed`` moves the token choice to the device sampler
+        (:mod:`llark_amd.m2t.sampling`, HF 4.29.2's processor order; ``top_k`` None or 0: off): draws are Philox under ``seed`` with the
+        batch row as stream id, and ``do_sample=False`` with a ``repetition_penalty`` is penalised greedy search."""
+        sampling = params_from_generate(do_sample, temperature, top_k, top_p, repetition_penalty, seed)
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
             return self._generate_ragged(input_ids, attention_mask, audio_encodings, max_new_tokens, do_sample, stopping_criteria,
-                                         eos_token_id, temperature)
+                                         eos_token_id, temperature, sampling)
         ids = input_ids.to(self.engine.device)
+        sampler = None
         eos = eos_token_id if eos_token_id is not None else getattr(self.generation_config, "eos_token_id", None)
         pad = getattr(self.generation_config, "pad_token_id", None)
         pad = eos if pad is None else pad
@@ -406,7 +415,12 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
                 logits = eng.forward_tokens(step_ids, segs, pos0=0, last_only=True)
             past = EngineCache(eng)
             scores = logits[:, -1]
-            if do_sample:
+            if sampling is not None:
+                if sampler is None:
+                    sampler = DeviceSampler(sampling, ids.shape[0], scores.shape[-1], ids.device)
+                    sampler.admit(range(ids.shape[0]), list(ids), range(ids.shape[0]))
+                nxt = sampler(scores).view(-1, 1)
+            elif do_sample:
                 probs = torch.softmax(scores / max(temperature, 1e-6), dim=-1)
                 nxt = torch.multinomial(probs, 1)
             else:
@@ -422,7 +436,7 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
         return ids
 
     def _generate_ragged(self, input_ids, attention_mask, audio_encodings, max_new_tokens, do_sample, stopping_criteria, eos_token_id,
-                         temperature):
+                         temperature, sampling=None):
         """generate() over a padded batch: row b is the sequence input_ids[b][mask[b]] at positions 0 .. len_b - 1 (HF's
         position_ids = cumsum(mask) - 1), one engine slot per row (prefill_slots / decode_slots).  Returns the HF layout: the input
         as given followed by the new tokens; rows that finished emit the pad token."""
@@ -463,6 +477,13 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
         out[:, :S] = ids_dev
         eng.init_slots(B)
         scores = eng.prefill_slots([r.to(eng.device) for r in rows], segs, range(B))
+        if sampling is not None:
+            sampler = DeviceSampler(sampling, B, scores.shape[-1], eng.device)
+            sampler.admit(range(B), rows, range(B))
+            do_sample = True                                                        # the callable below decides, penalised greedy included
+
+            def sample(scores):
+                return sampler(scores, state=eng.slot_state)
         nxt, _ = eng.advance_slots(scores, eos_k, pad_k, out[:, S], sample(scores) if do_sample else None, advance=False)
         n = 1
         while True:

@@ -28,6 +28,7 @@ from .. import ops
 from . import AudioEncoderConfig
 from .llamav2 import EngineCache, plan_audio_splice
 from .mpt_engine import HipMptEngine, MptDims
+from .sampling import DeviceSampler, params_from_generate
 from .special_tokens import DEFAULT_AUDIO_END_TOKEN, DEFAULT_AUDIO_PATCH_TOKEN, DEFAULT_AUDIO_START_TOKEN
 
 ATTN_DEFAULTS = dict(attn_type="multihead_attention", attn_pdrop=0.0, attn_impl="torch", qk_ln=False, clip_qkv=None, softmax_scale=None,
@@ -293,21 +294,34 @@ class WrappedMPTForCausalLM(nn.Module):
 
     @torch.no_grad()
     def generate(self, input_ids=None, audio_encodings=None, max_new_tokens: int = 20, stopping_criteria=None, eos_token_id=None,
-                 attention_mask=None, pad_token_id=None, **kwargs):
-        """Greedy loop driven by :meth:`prepare_inputs_for_generation` (prompt with audio once, then one token per step).  An
+                 attention_mask=None, pad_token_id=None, do_sample: bool = False, temperature: float = 1.0, top_k: Optional[int] = None,
+                 top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, seed: Optional[int] = None, **kwargs):
+        """Generation loop driven by :meth:`prepare_inputs_for_generation` (prompt with audio once, then one token per step).  An
         ``attention_mask`` with zeros (left- or right-padded) runs every row as if it were alone on the engine's ragged slot mode
-        (:meth:`_generate_ragged`); ``None`` or all ones takes this uniform path and never enters the slot mode."""
+        (:meth:`_generate_ragged`); ``None`` or all ones takes this uniform path and never enters the slot mode.
+
+        Greedy by default.  ``do_sample`` (with ``temperature``, ``top_k``, ``top_p``, ``repetition_penalty``, ``seed``; ``top_k`` None or
+        0: off) chooses every token with the device sampler (:mod:`llark_amd.m2t.sampling`, HF 4.29.2's processor order; Philox draws
+        under ``seed``, the batch row as stream id); ``do_sample=False`` with a ``repetition_penalty`` is penalised greedy search."""
+        sampling = params_from_generate(do_sample, temperature, top_k, top_p, repetition_penalty, seed, always=bool(do_sample))
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
             return self._generate_ragged(input_ids, attention_mask, audio_encodings, max_new_tokens, stopping_criteria, eos_token_id,
-                                         pad_token_id)
+                                         pad_token_id, sampling)
         ids = input_ids.to(self.engine.device)
         past = None
+        sampler = None
         for _ in range(max_new_tokens):
             inp = self.prepare_inputs_for_generation(ids, past_key_values=past, audio_encodings=audio_encodings)
             out = self.forward(inp["input_ids"], past_key_values=inp["past_key_values"], audio_encodings=inp["audio_encodings"])
             past = out.past_key_values
             scores = out.logits[:, -1]
-            nxt = scores.argmax(-1, keepdim=True)
+            if sampling is not None:
+                if sampler is None:
+                    sampler = DeviceSampler(sampling, ids.shape[0], scores.shape[-1], ids.device)
+                    sampler.admit(range(ids.shape[0]), list(ids), range(ids.shape[0]))
+                nxt = sampler(scores).view(-1, 1)
+            else:
+                nxt = scores.argmax(-1, keepdim=True)
             ids = torch.cat((ids, nxt), dim=1)
             if eos_token_id is not None and bool((nxt == eos_token_id).all()):
                 break
@@ -315,7 +329,8 @@ class WrappedMPTForCausalLM(nn.Module):
                 break
         return ids
 
-    def _generate_ragged(self, input_ids, attention_mask, audio_encodings, max_new_tokens, stopping_criteria, eos_token_id, pad_token_id):
+    def _generate_ragged(self, input_ids, attention_mask, audio_encodings, max_new_tokens, stopping_criteria, eos_token_id, pad_token_id,
+                         sampling=None):
         """generate() over a padded batch (``WrappedLlamav2ForCausalLM._generate_ragged``): row b is the sequence
         input_ids[b][mask[b]] at positions 0 .. len_b - 1, one engine slot per row (prefill_slots / decode_slots).  Returns the HF
         layout: the input as given followed by the new tokens; a row that emitted EOS continues with the pad token (EOS when none)."""
@@ -346,7 +361,14 @@ class WrappedMPTForCausalLM(nn.Module):
         out[:, :S] = ids_dev
         eng.init_slots(B)
         scores = eng.prefill_slots([r.to(eng.device) for r in rows], segs, range(B))
-        nxt, _ = eng.advance_slots(scores, eos_k, pad_k, out[:, S], advance=False)
+        sample = None
+        if sampling is not None:
+            sampler = DeviceSampler(sampling, B, scores.shape[-1], eng.device)
+            sampler.admit(range(B), rows, range(B))
+
+            def sample(scores):
+                return sampler(scores, state=eng.slot_state)
+        nxt, _ = eng.advance_slots(scores, eos_k, pad_k, out[:, S], None if sample is None else sample(scores), advance=False)
         n = 1
         while True:
             if use_eos and all(st != ops.ROW_ACTIVE for st in eng.slot_state_host):
@@ -355,6 +377,6 @@ class WrappedMPTForCausalLM(nn.Module):
                 break
             if n == max_new_tokens:
                 break
-            nxt, _, scores = eng.decode_slots(nxt, eos_k, pad_k, out[:, S + n])
+            nxt, _, scores = eng.decode_slots(nxt, eos_k, pad_k, out[:, S + n], sample)
             n += 1
         return out[:, : S + n]

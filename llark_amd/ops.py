@@ -1119,6 +1119,49 @@ def decode_advance_rows(logits: Optional[torch.Tensor], state: torch.Tensor, nex
                                                int(eos), int(pad), _stream()), "decode_advance_rows")
 
 
+def sample_rows(logits: torch.Tensor, choice: torch.Tensor, *, vocab: Optional[int] = None, state: Optional[torch.Tensor] = None,
+                slot_of_row: Optional[torch.Tensor] = None, seen: Optional[torch.Tensor] = None, do_sample: bool = True,
+                temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0,
+                u: Optional[torch.Tensor] = None, seed: int = 0, draws: Optional[torch.Tensor] = None,
+                stream_id: Optional[torch.Tensor] = None, kept: Optional[torch.Tensor] = None, thresh: Optional[torch.Tensor] = None,
+                fallbacks: Optional[torch.Tensor] = None, slots: Optional[int] = None) -> torch.Tensor:
+    """Token of every row of fp32 ``logits`` [rows, >= vocab] into ``choice`` (int64 [rows]) in one launch: repetition penalty over the
+    ``seen`` bitmaps (int32 [slots, >= ceil(vocab / 32)]) -> temperature -> top-k -> top-p -> draw, HF 4.29.2's order; ``do_sample=False``
+    is the penalised greedy token.  Row r belongs to slot ``slot_of_row[r]`` (identity without it); with ``state`` (int32 [slots]) only
+    ROW_ACTIVE slots are touched.  The draw takes ``u[r]`` or Philox4x32-10 under (``seed``; ``draws[slot]``, ``stream_id[slot]``);
+    the token's seen bit is set and ``draws[slot]`` advances.  Contract: include/llark_hip.h (llark_sample_rows)."""
+    i32 = torch.int32
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    rows = logits.shape[0]
+    vocab = logits.shape[1] if vocab is None else int(vocab)
+    assert 0 < vocab <= logits.shape[1] and choice.numel() == rows
+    per_slot = [t for t in (state, draws, stream_id) if t is not None]
+    if slots is None:
+        slots = seen.shape[0] if seen is not None else per_slot[0].numel() if per_slot else rows
+    assert all(t.numel() == slots for t in per_slot) and (seen is None or (seen.dim() == 2 and seen.shape[0] == slots and seen.stride(1) == 1))
+    assert all(t is None or t.numel() == rows for t in (slot_of_row, u, kept, thresh))
+    check(_lib.lib().llark_sample_rows(_dev(logits, "logits", torch.float32, contiguous=False), logits.stride(0), vocab, rows, int(slots),
+                                       _opt(state, "state", i32), _opt(slot_of_row, "slot_of_row", i32),
+                                       _opt(seen, "seen", i32, contiguous=False), _ld(seen), int(bool(do_sample)), float(temperature),
+                                       int(top_k), float(top_p), float(repetition_penalty), _opt(u, "u", torch.float32), int(seed),
+                                       _opt(draws, "draws", i32), _opt(stream_id, "stream_id", torch.int64),
+                                       _dev(choice, "choice", torch.int64), _opt(kept, "kept", i32), _opt(thresh, "thresh", torch.float32),
+                                       _opt(fallbacks, "fallbacks", i32), _stream()), "sample_rows")
+    return choice
+
+
+def seen_mark_rows(ids: torch.Tensor, offs: torch.Tensor, lens: torch.Tensor, seen: torch.Tensor, vocab: int,
+                   slot_of_row: Optional[torch.Tensor] = None) -> None:
+    """Sets, in the ``seen`` bitmap (int32 [slots, >= ceil(vocab / 32)]) of slot ``slot_of_row[r]`` (identity without it), the bits of
+    the token list ``ids[offs[r] : offs[r] + lens[r]]`` (ids int64, flat; offs / lens int32 [rows]); ids outside [0, vocab) are ignored."""
+    i32 = torch.int32
+    rows = offs.numel()
+    assert lens.numel() == rows and (slot_of_row is None or slot_of_row.numel() == rows) and seen.dim() == 2 and seen.stride(1) == 1
+    check(_lib.lib().llark_seen_mark_rows(_dev(ids, "ids", torch.int64), ids.numel(), _dev(offs, "offs", i32), _dev(lens, "lens", i32),
+                                          _opt(slot_of_row, "slot_of_row", i32), rows, seen.shape[0], int(vocab),
+                                          _dev(seen, "seen", i32, contiguous=False), seen.stride(0), _stream()), "seen_mark_rows")
+
+
 # ------------------------------------------------------------------------------------------------
 # MPT
 # ------------------------------------------------------------------------------------------------

@@ -21,6 +21,12 @@ Shared prompt prefixes: consecutive examples are the questions of one clip (one 
 (slots, questions per clip) cell runs the inflight schedule with share_prefix off and on, alternating which goes first, and records
 clips/s, the decode step with every slot active, the attention launches' device time per step (ops kernel tags) and the time per
 example of filling the slots.  ONE JSON line on stdout (each cell also on stderr as it finishes).
+
+    python scripts/bench_generate_inflight.py --sampling [--slots 16,64]
+Greedy against sampled decode step, same run: every slot active, blocks of 16 steps alternate between the greedy step and the step
+whose tokens come from the device sampler (temperature 0.7, top-k 200, top-p 0.95, repetition penalty 1.3; one more launch per step),
+which kind goes first alternating too.  Per slot count: the median block of either kind, the spread of the blocks, and the sampled
+step's excess as a fraction of the greedy step.  ONE JSON line.
 """
 import argparse
 import json
@@ -252,8 +258,55 @@ def main_shared(args, slot_list):
     print(json.dumps(res), flush=True)
 
 
+def main_sampling(args, slot_list):
+    import statistics
+
+    from llark_amd.m2t.sampling import DeviceSampler, SamplingParams
+    steps, blocks = 16, 8
+    examples = make_examples(64, args.seed)
+    max_seq = max(ids.numel() for ids, _, _ in examples) + 8 + steps * (2 * blocks + 2)
+    model = RandomLlama(args.precision, max(slot_list), max_seq)
+    eng = model.engine
+    sp = SamplingParams(do_sample=True, temperature=0.7, top_k=200, top_p=0.95, repetition_penalty=1.3, seed=args.seed)
+    res = {"bench": "generate_inflight_sampling", "model": "llama2-7b dims, random weights", "precision": args.precision,
+           "sampling": dict(temperature=0.7, top_k=200, top_p=0.95, repetition_penalty=1.3), "steps_per_block": steps, "blocks": blocks, "slots": {}}
+    for n in slot_list:
+        eng.init_slots(n)
+        rows = [examples[i % len(examples)] for i in range(n)]
+        logits = eng.prefill_slots([r[0].cuda() for r in rows], [(k, 1, r[1].cuda()) for k, r in enumerate(rows)], range(n))
+        sampler = DeviceSampler(sp, n, logits.shape[-1], eng.device)
+        sampler.admit(range(n), [r[0] for r in rows], range(n))
+        kinds = {"greedy": None, "sampled": lambda lg: sampler(lg, state=eng.slot_state)}
+        ids = logits.argmax(-1)
+
+        def block(kind):
+            nonlocal ids
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                ids, _, _ = eng.decode_slots(ids, sample=kinds[kind])
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / steps * 1e3
+
+        block("greedy"), block("sampled")                        # warm
+        ms = {"greedy": [], "sampled": []}
+        for b in range(blocks):
+            for kind in (("greedy", "sampled") if b % 2 == 0 else ("sampled", "greedy")):
+                ms[kind].append(block(kind))
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        cell = {"greedy_step_ms": round(med["greedy"], 4), "sampled_step_ms": round(med["sampled"], 4),
+                "greedy_min_max_ms": [round(min(ms["greedy"]), 4), round(max(ms["greedy"]), 4)],
+                "sampled_min_max_ms": [round(min(ms["sampled"]), 4), round(max(ms["sampled"]), 4)],
+                "excess_fraction_of_step": round(med["sampled"] / med["greedy"] - 1.0, 4), "fallback_rows": sampler.fallback_count()}
+        res["slots"][str(n)] = cell
+        print(json.dumps({str(n): cell}), file=sys.stderr, flush=True)
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--sampling", action="store_true", help="same-run A/B of the decode step with every slot active: greedy against the "
+                    "device sampler (default slot counts 16,64)")
     ap.add_argument("--questions-per-clip", default=None, help="e.g. 1,4,8: consecutive examples share an encoding, an audio-first prefix "
                     "and a prefix key (inflight schedule only; one result cell per slot count and value)")
     ap.add_argument("--share-prefix", action="store_true", help="with --questions-per-clip: run every cell with share_prefix off and on")
@@ -268,6 +321,8 @@ def main():
     slot_list = [int(x) for x in args.slots.split(",") if x]
     if not slot_list or any(not 1 <= n <= 64 for n in slot_list):
         ap.error(f"--slots takes counts in 1 .. 64, got {args.slots!r}")
+    if args.sampling:
+        return main_sampling(args, [16, 64] if args.slots == ap.get_default("slots") else slot_list)
     if args.questions_per_clip:
         return main_shared(args, slot_list)
     if args.share_prefix:
