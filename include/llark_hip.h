@@ -587,6 +587,28 @@ int llark_sample_rows(const float* logits, int ldl, int vocab, int rows, int slo
                       int* fallbacks, llark_stream_t stream);
 int llark_seen_mark_rows(const int64_t* ids, long long n_ids, const int* offs, const int* lens, const int* slot_of_row, int rows,
                          int slots, int vocab, unsigned* seen, int ld_seen, llark_stream_t stream);
+/* Token log-probabilities on the device (csrc/logprob.hip): what the model's own distribution -- log-softmax of the RAW logits, before any
+ * repetition penalty, temperature, top-k or top-p -- gives the token tokens[r], for the rows of a decode step, a prefill or a scored text.
+ *   llark_token_logprob_rows: one workgroup per row r of logits fp32 [rows][ldl] (columns >= vocab are never read).  slot = slot_of_row[r]
+ *     (int32 [rows], NULL: slot = r; rows map to DISTINCT slots).  A row is skipped -- nothing of it is read, nothing is written for it --
+ *     when its slot is outside [0, slots), when state != NULL (int32 [slots] of LLARK_ROW_*) and the slot is not LLARK_ROW_ACTIVE, or when
+ *     tokens[r] (int64 [rows]) is outside [0, vocab): a negative token is the caller's "no target here" mark.  Otherwise, with t =
+ *     tokens[r], M = max_i l_i and S = sum_i expf(l_i - M) over i < vocab, all in fp32:
+ *       logprob[r] = (l_t - M) - logf(S);  rank[r] (nullable) = the number of i with l_i > l_t, exact; 0: t is a greedy token.
+ *       A -inf logit adds 0 to S; a target whose logit is -inf gets -inf.  A row that holds a NaN, or whose maximum is +-inf, gets
+ *       logprob[r] = NaN and rank[r] = -1.
+ *     Per-slot history (hist fp32 [slots][ld_hist], count int32 [slots], total fp32 [slots]; each nullable, hist needs count): when
+ *       count[slot] < ld_hist, hist[slot][count[slot]] = logprob[r]; then total[slot] += logprob[r] and count[slot] += 1.  The caller
+ *       zeroes count and total when a slot starts a new sequence, and reads a finished sequence's history in one transfer.
+ *     S is summed in a fixed order (thread tid takes the columns tid, tid + 1024, ... in order; a butterfly over the 64 lanes; the 16
+ *       wave sums in wave order: at most ceil(vocab / 1024) + 21 additions on a path): logprob[r] is bit-reproducible and depends on
+ *       the row's vocab floats and on t alone, not on r, the slot, rows, ldl or the row's alignment.  Any vocab; a row of up to 51 200
+ *       columns is read from memory once.
+ *     LLARK_ERR_INVALID before any launch: a null logits / tokens / logprob, rows, slots or vocab <= 0, ldl < vocab, rows > slots without
+ *     slot_of_row, hist without count, ld_hist <= 0 with hist. */
+int llark_token_logprob_rows(const float* logits, int ldl, int vocab, int rows, int slots, const int* state, const int* slot_of_row,
+                             const int64_t* tokens, float* logprob, int* rank, float* hist, int ld_hist, int* count, float* total,
+                             llark_stream_t stream);
 /* MPT ragged decode step, the whole attention front in one launch (m2t/llava/model/mpt/attention.py: qkv.clamp_ -> q_ln / k_ln ->
  * head split -> attention with the ALiBi bias; replaces llark_clamp_f32 + 2 x llark_layernorm_f32 + llark_attn_decode_rope_bf16_rows
  * with identity tables).  qkv fp32 [batch][ldq], laid out q | k | v with nh*128 columns each, is READ ONLY.  Workgroup (h, b) reads

@@ -109,23 +109,31 @@ class InflightScheduler:
 
     ``sampling``: the backend draws its tokens (:class:`llark_amd.m2t.sampling.DeviceSampler`) and every ``prefill`` call also gets
     ``indices=`` (the examples' input indices: their random streams) and ``whole=`` (their full prompts -- what a forked slot has seen
-    although only its suffix is prefilled).  Off (the default), the backend's signature is what it was."""
+    although only its suffix is prefilled).  Off (the default), the backend's signature is what it was.
+
+    ``logprobs``: the backend records the log-probability of every token it hands out -- log-softmax of the model's raw logits; no
+    repetition penalty, temperature, top-k or top-p is applied, for sampled tokens too -- and ``run`` yields ``(index, ids, logprobs)``
+    with one entry per generated token, the EOS or keyword token included.  ``backend.take_logprobs(finished)`` (a list of 1-D
+    tensors in the order of ``finished``) is called just before ``backend.release(finished)``.  Off (the default), the backend sees
+    no new call and ``run`` yields pairs."""
 
     def __init__(self, backend, n_slots: int, max_new_tokens: int = 512, eos: Optional[int] = None, stop_fn=None,
-                 share_prefix: bool = False, min_shared: int = MIN_SHARED, sampling: bool = False):
+                 share_prefix: bool = False, min_shared: int = MIN_SHARED, sampling: bool = False, logprobs: bool = False):
         if n_slots < 1:
             raise ValueError(f"n_slots must be >= 1, got {n_slots}")
         self.backend, self.n_slots, self.max_new_tokens = backend, n_slots, max_new_tokens
         self.share_prefix = bool(share_prefix) and hasattr(backend, "fork")
         self.min_shared = min_shared
         self.sampling = bool(sampling)
+        self.logprobs = bool(logprobs)
         self.eos = eos if eos is not None and eos >= 0 else None
         self.stop_fn = stop_fn                    # (prompt ids, generated ids) -> bool: keyword stop; may keep state per row
         self.trace: List[Tuple] = []
 
     def run(self, examples: Iterable[Sequence[Any]]) -> Iterator[Tuple[int, torch.Tensor]]:
         """examples: (prompt_ids, encoding[, max_new_tokens[, prefix_key]]).  Yields (input index, prompt + generated ids) as rows finish; rows
-        finishing in the same step come out in input order."""
+        finishing in the same step come out in input order.  With ``logprobs``: (input index, ids, log-probabilities of the generated
+        tokens under the model's raw logits)."""
         it = enumerate(examples)
         exhausted = False
         table: List[Optional[Dict[str, Any]]] = [None] * self.n_slots
@@ -218,13 +226,21 @@ class InflightScheduler:
                 finished.append(b)
         if not finished:
             return []
+        lps = self.backend.take_logprobs(finished) if self.logprobs else None
         self.backend.release(finished)
         outs = []
-        for b in finished:
+        for i, b in enumerate(finished):
             row = table[b]
             table[b] = None
             self.trace.append(("done", b, row["index"]))
-            outs.append((row["index"], torch.cat((row["prompt"], torch.tensor(row["out"], dtype=torch.int64)))))
+            ids = torch.cat((row["prompt"], torch.tensor(row["out"], dtype=torch.int64)))
+            if lps is None:
+                outs.append((row["index"], ids))
+            else:
+                lp = torch.as_tensor(lps[i], dtype=torch.float32).reshape(-1)
+                if lp.numel() != len(row["out"]):
+                    raise RuntimeError(f"slot {b}: {lp.numel()} log-probabilities for {len(row['out'])} generated tokens")
+                outs.append((row["index"], ids, lp))
         return sorted(outs, key=lambda o: o[0])
 
 
@@ -233,9 +249,12 @@ class EngineSlots:
     ``release_slots`` of ``HipLlamaEngine`` or ``HipMptEngine``) of a ``WrappedLlamav2ForCausalLM`` or ``WrappedMPTForCausalLM``.  The
     MPT wrapper splices audio by its patch tokens (``audio_patch_branch``) and its engine has no shared-prefix form (``init_slots``
     raises ``NotImplementedError``).  ``sampling`` (a :class:`llark_amd.m2t.sampling.SamplingParams`): tokens come from the device
-    sampler, whose stream id is the example's input index."""
+    sampler, whose stream id is the example's input index.  ``logprobs``: every token handed out -- the first one from the refill's
+    prefill logits, the others from the decode step's -- gets its log-probability under the model's raw logits (log-softmax; no
+    repetition penalty, temperature, top-k or top-p, for sampled tokens too) appended to its slot's history on the device
+    (:class:`llark_amd.m2t.logprob.LogprobTracker`, one launch per step); ``take_logprobs(slots)`` reads finished slots' histories."""
 
-    def __init__(self, model, n_slots: int, share_prefix: bool = False, sampling=None):
+    def __init__(self, model, n_slots: int, share_prefix: bool = False, sampling=None, logprobs: bool = False):
         from .llamav2 import plan_audio_splice
 
         self._plan = plan_audio_splice
@@ -249,6 +268,8 @@ class EngineSlots:
         self.ids = torch.zeros((n_slots,), dtype=torch.int64, device=self.eng.device)
         self.sampling = sampling if sampling is not None and sampling.active else None
         self.sampler = None                                       # built at the first prefill, which tells the logits' width
+        self.logprobs = bool(logprobs)
+        self.tracker = None                                       # likewise
         cfg = model.get_model().audio_encoder_config
         self.audio_token_ids = tuple(int(t) for t in (getattr(cfg, name, None) for name in ("audio_start_token", "audio_end_token", "audio_patch_token"))
                                      if t is not None)
@@ -277,18 +298,39 @@ class EngineSlots:
             first = self.sampler(logits, state=eng.slot_state, slot_of_row=list(slots))
         else:
             first = logits.argmax(-1)                              # what generate() picks after the prompt
+        if self.logprobs:
+            if self.tracker is None:
+                from .logprob import LogprobTracker
+
+                self.tracker = LogprobTracker(eng.n_slots, logits.shape[-1], eng.device, eng.smax)
+            self.tracker.admit(slots)
+            self.tracker(logits, first, state=eng.slot_state, slot_of_row=list(slots))
         self.ids[torch.tensor(slots, dtype=torch.long, device=eng.device)] = first
         return first.cpu().tolist()
 
     def decode(self):
-        if self.sampler is not None:
+        if self.sampler is not None or self.tracker is not None:
             self.ids, host, _ = self.eng.decode_slots(self.ids, sample=self._sample)
         else:
             self.ids, host, _ = self.eng.decode_slots(self.ids)
         return host.tolist()
 
     def _sample(self, logits):
-        return self.sampler(logits, state=self.eng.slot_state)
+        if self.sampler is not None:
+            tokens = self.sampler(logits, state=self.eng.slot_state)
+        else:                                                      # the advance kernel's own rule: the first maximal index
+            from .. import ops
+
+            tokens = ops.sample_rows(logits, torch.zeros((logits.shape[0],), dtype=torch.int64, device=logits.device),
+                                     state=self.eng.slot_state, do_sample=False, repetition_penalty=1.0)
+        if self.tracker is not None:
+            self.tracker(logits, tokens, state=self.eng.slot_state)
+        return tokens
+
+    def take_logprobs(self, slots):
+        if self.tracker is None:
+            raise RuntimeError("EngineSlots: built without logprobs=True")
+        return self.tracker.take(slots)
 
     def release(self, slots):
         self.eng.release_slots(slots)
@@ -299,7 +341,7 @@ class EngineSlots:
 @torch.no_grad()
 def generate_inflight(model, examples: Iterable[Sequence[Any]], slots: int = 8, max_new_tokens: int = 512,
                       keywords: Sequence[str] = ("###",), tokenizer=None, trace: Optional[list] = None,
-                      share_prefix: bool = False, sampling=None) -> Iterator[Tuple[int, torch.Tensor]]:
+                      share_prefix: bool = False, sampling=None, return_logprobs: bool = False) -> Iterator[Tuple[int, torch.Tensor]]:
     """Generation (greedy unless ``sampling``) with in-flight slot refill.  ``examples`` yields ``(prompt_ids, encoding[, max_new_tokens[, prefix_key]])`` with prompts
     of any length; up to ``slots`` of them decode together, each at its own KV-cache length, and a finished row's slot is refilled
     from the iterable (contiguous free slots prefilled as one batch) while the others keep decoding.  Stops per row as in
@@ -310,14 +352,25 @@ def generate_inflight(model, examples: Iterable[Sequence[Any]], slots: int = 8, 
     siblings' slots, and read once per group by the decode step (:class:`InflightScheduler`, ``HipLlamaEngine.fork_slots``).
     ``sampling``: a :class:`llark_amd.m2t.sampling.SamplingParams`; tokens are then chosen by the device sampler with the example's
     index as its random stream, so a completion depends neither on the slot the example landed in nor on ``slots`` (a model's own
-    ``slot_backend`` is greedy: sampling with one is refused)."""
+    ``slot_backend`` is greedy: sampling with one is refused).  ``return_logprobs``: yields ``(index, ids, logprobs)`` instead;
+    ``logprobs`` (1-D fp32, CPU) has one entry per generated token, ``ids.numel() - prompt.numel()`` of them, the EOS or keyword token
+    included.  They are log-probabilities of the MODEL's distribution: log-softmax of the raw logits, computed on the device in the
+    step's own launch sequence (``llark_token_logprob_rows``); repetition penalty, temperature, top-k and top-p are not applied, for
+    sampled tokens too.  Refused with a model's own ``slot_backend`` as sampling is."""
     if keywords and tokenizer is None:
         raise ValueError("generate_inflight: keyword stopping needs the tokenizer")
     make = getattr(model, "slot_backend", None)
     sampling = sampling if sampling is not None and sampling.active else None
     if sampling is not None and make is not None:
         raise ValueError("generate_inflight: sampling needs the engine's own slot backend; this model provides slot_backend()")
-    backend = make(slots) if make is not None else EngineSlots(model, slots, share_prefix, sampling)
+    if return_logprobs and make is not None:
+        raise ValueError("generate_inflight: return_logprobs needs the engine's own slot backend; this model provides slot_backend()")
+    if make is not None:
+        backend = make(slots)
+    elif return_logprobs:
+        backend = EngineSlots(model, slots, share_prefix, sampling, logprobs=True)
+    else:
+        backend = EngineSlots(model, slots, share_prefix, sampling)
     eos = getattr(getattr(model, "generation_config", None), "eos_token_id", None)
     stop_fn = None
     if keywords:
@@ -325,10 +378,72 @@ def generate_inflight(model, examples: Iterable[Sequence[Any]], slots: int = 8, 
             if row["stop"] is None:
                 row["stop"] = KeywordsStoppingCriteria(keywords=list(keywords), tokenizer=tokenizer, input_ids=row["prompt"][None])
             return bool(row["stop"](torch.cat((row["prompt"], gen))[None], None))
-    sched = InflightScheduler(backend, slots, max_new_tokens, eos, stop_fn, share_prefix=share_prefix, sampling=sampling is not None)
+    sched = InflightScheduler(backend, slots, max_new_tokens, eos, stop_fn, share_prefix=share_prefix, sampling=sampling is not None,
+                              **(dict(logprobs=True) if return_logprobs else {}))
     if trace is not None:
         sched.trace = trace
     yield from sched.run(examples)
+
+
+@torch.no_grad()
+def score_continuations(model, prompt_ids, encoding, continuations: Sequence[Any], logits_sink: Optional[list] = None) -> List[torch.Tensor]:
+    """Teacher-forced scoring of candidate answers after one prompt: per candidate (a 1-D sequence of token ids, not empty), the
+    log-probability of each of its tokens given the prompt (with ``encoding`` spliced in, or None) and the candidate's earlier
+    tokens -- a 1-D fp32 CPU tensor of the candidate's length; its ``sum()`` ranks the candidates of a closed answer set
+    (giantsteps key / tempo, gtzan genre), its ``mean()`` is the length-normalised score.
+
+    They are log-probabilities of the MODEL's distribution: log-softmax of the raw logits; no repetition penalty, temperature, top-k
+    or top-p exists on this path.  Each candidate is one row ``prompt + continuation`` through ``engine.forward_tokens`` with full
+    logits; then ONE ``ops.token_logprob_rows`` launch over all B * S rows of the call, whose ``tokens`` are the ids shifted by one and
+    -1 everywhere outside a candidate's own span (its first scored row is the prompt's last position), so prompt rows and pad rows are
+    skipped.  Llama runs the candidates as right-padded batches of up to the engine's ``max_batch`` (causal attention never lets a
+    valid position see a pad); MPT's forward takes no padded batch, so candidates of equal length share a batch and the rest run
+    singly.  ``logits_sink``: a list that receives ``(logits [B * S, V], tokens [B * S])`` of every call (device tensors)."""
+    from .. import ops
+    from .llamav2 import plan_audio_splice
+
+    eng = model.engine
+    dev = eng.device
+    prompt = torch.as_tensor(prompt_ids, dtype=torch.int64).reshape(-1).to(dev)
+    P = int(prompt.numel())
+    conts = [torch.as_tensor(c, dtype=torch.int64).reshape(-1).to(dev) for c in continuations]
+    if P < 1 or any(c.numel() < 1 for c in conts):
+        raise ValueError("score_continuations: the prompt and every continuation need at least one token")
+    patch = bool(getattr(model, "audio_patch_branch", False))              # the MPT wrapper
+    plan_kw = dict(patch_branch=True) if patch else {}
+    cfg = model.get_model().audio_encoder_config
+    feats = None if encoding is None else torch.as_tensor(encoding).to(device=dev, dtype=torch.float32)
+    order = sorted(range(len(conts)), key=lambda i: conts[i].numel()) if patch else list(range(len(conts)))
+    batches: List[List[int]] = []
+    for i in order:
+        if batches and len(batches[-1]) < eng.max_batch and (not patch or conts[batches[-1][0]].numel() == conts[i].numel()):
+            batches[-1].append(i)
+        else:
+            batches.append([i])
+    pending = []
+    for batch in batches:
+        B, S = len(batch), P + max(conts[i].numel() for i in batch)
+        ids = torch.zeros((B, S), dtype=torch.int64, device=dev)
+        tokens = torch.full((B, S), -1, dtype=torch.int64, device=dev)
+        for b, i in enumerate(batch):
+            n = conts[i].numel()
+            ids[b, :P] = prompt
+            ids[b, P: P + n] = conts[i]
+            tokens[b, P - 1: P - 1 + n] = conts[i]
+        segs = [] if feats is None else list(plan_audio_splice(ids, [feats] * B, cfg, False, **plan_kw))
+        logits = eng.forward_tokens(ids, segs).reshape(B * S, -1)
+        tokens = tokens.view(-1)
+        if logits_sink is not None:
+            logits_sink.append((logits, tokens))
+        lp = torch.full((B * S,), float("nan"), dtype=torch.float32, device=dev)
+        ops.token_logprob_rows(logits, tokens, lp)
+        pending.append((batch, lp.view(B, S)))
+    out: List[Optional[torch.Tensor]] = [None] * len(conts)
+    for batch, lp in pending:
+        host = lp.cpu()
+        for b, i in enumerate(batch):
+            out[i] = host[b, P - 1: P - 1 + conts[i].numel()].clone()
+    return out
 
 
 def _rows_to_records(example_ids, prompt, outs, end_seq, tokenizer) -> List[Dict[str, str]]:
@@ -434,12 +549,13 @@ def infer_from_audio(encoder, model, tokenizer, clips: Iterable[Tuple[str, np.nd
 
 
 SHARD_COLUMNS = ["example_id", "prompt_text", "original_completion_text", "model_completion_text"]
+LOGPROB_COLUMNS = ["sum_logprob", "mean_logprob", "n_tokens"]
 
 
 def infer_from_shards(model, tokenizer, shards: str, multimodal_cfg: Dict[str, Any], end_seq: Sequence[int], outfile: Optional[str] = None,
                       slots: int = 8, max_samples: Optional[int] = None, max_new_tokens: int = 512, prompt: Optional[str] = None,
                       seed: int = 0, allow_pickle: bool = False, header: str = DEFAULT_CONVERSATION_HEADER,
-                      share_prefix: bool = False, sampling=None) -> List[Dict[str, str]]:
+                      share_prefix: bool = False, sampling=None, logprobs: bool = False) -> List[Dict[str, str]]:
     """Local tar shards -> CSV under the contract of ``scripts/inference/infer_from_webdataset.py:51-151``: every (question,
     answer) pair of a sample is one example whose prompt is its own human turn up to "### Assistant:" (audio placeholder first
     or last by a draw seeded with ``seed``); ``prompt`` overrides every question (the reference's ``--prompt``: audio first).
@@ -447,7 +563,10 @@ def infer_from_shards(model, tokenizer, shards: str, multimodal_cfg: Dict[str, A
     (the pair's answer) and ``model_completion_text``, in input order.  ``max_samples`` caps the number of examples.  All
     generation runs through :func:`generate_inflight` with ``slots`` batch slots.  ``share_prefix``: the questions of one sample
     (its tar key is their ``prefix_key``) share the K/V of their common leading tokens when the audio placeholder comes first.
-    ``sampling``: a :class:`llark_amd.m2t.sampling.SamplingParams` (its ``seed`` is the draws'; ``seed`` here shuffles the questions)."""
+    ``sampling``: a :class:`llark_amd.m2t.sampling.SamplingParams` (its ``seed`` is the draws'; ``seed`` here shuffles the questions).
+    ``logprobs``: every record also gets ``sum_logprob``, ``mean_logprob`` and ``n_tokens`` over ALL generated tokens (the stop keyword or
+    EOS included, although the completion text drops it): log-probabilities of the model's distribution -- log-softmax of the raw
+    logits; repetition penalty, temperature, top-k and top-p are not applied, for sampled tokens too."""
     from .data import element_to_conversations, expand_urls, iter_tar_samples
 
     rng = random.Random(seed)
@@ -470,18 +589,27 @@ def infer_from_shards(model, tokenizer, shards: str, multimodal_cfg: Dict[str, A
                              "original_completion_text": tokenizer.decode(extract_response_tokens(ex["input_ids"], end_seq))})
                 yield ids, enc, None, conv["id"]
 
-    outs: Dict[int, torch.Tensor] = dict(generate_inflight(model, examples(), slots=slots, max_new_tokens=max_new_tokens, tokenizer=tokenizer,
-                                                           share_prefix=share_prefix, sampling=sampling))
+    outs: Dict[int, torch.Tensor] = {}
+    lps: Dict[int, torch.Tensor] = {}
+    for item in generate_inflight(model, examples(), slots=slots, max_new_tokens=max_new_tokens, tokenizer=tokenizer,
+                                  share_prefix=share_prefix, sampling=sampling, **(dict(return_logprobs=True) if logprobs else {})):
+        outs[item[0]] = item[1]
+        if logprobs:
+            lps[item[0]] = item[2]
     records = []
     for i, m in enumerate(meta):
-        records.append(dict(m, model_completion_text=tokenizer.decode(extract_response_tokens(outs[i], end_seq))))
+        rec = dict(m, model_completion_text=tokenizer.decode(extract_response_tokens(outs[i], end_seq)))
+        if logprobs:
+            lp = lps[i].double()
+            rec.update(sum_logprob=float(lp.sum()), mean_logprob=float(lp.mean()), n_tokens=int(lp.numel()))
+        records.append(rec)
     if outfile:
         import pandas as pd
 
         d = os.path.dirname(outfile)
         if d and not os.path.exists(d):
             os.makedirs(d)
-        pd.DataFrame(records, columns=SHARD_COLUMNS).to_csv(outfile, index=False)
+        pd.DataFrame(records, columns=SHARD_COLUMNS + (LOGPROB_COLUMNS if logprobs else [])).to_csv(outfile, index=False)
     return records
 
 
@@ -569,7 +697,7 @@ def main_shards(argv=None):
     """``shards`` mode, with the flags of the reference's ``scripts/inference/infer_from_webdataset.py:154-190`` (+ ``--slots``):
     python -m llark_amd.m2t.infer_driver shards --model_name_or_path <dir> --eval_data_path "shards-{000000..000021}.tar" \
         --outfile results/infer.csv [--prompt "Describe ..."] [--max-samples N] [--max_new_tokens 2048] [--slots 8] [--allow-pickle]
-        [--share-prefix] [--do-sample --temperature 0.8 --top-k 50 --top-p 0.9 --sample-seed 0] [--repetition-penalty 1.3]
+        [--share-prefix] [--do-sample --temperature 0.8 --top-k 50 --top-p 0.9 --sample-seed 0] [--repetition-penalty 1.3] [--logprobs]
     ``--allow-pickle``: read ``.pyd`` (pickled) encodings -- unpickling runs code, pass it only for shards you trust."""
     import argparse
 
@@ -594,6 +722,8 @@ def main_shards(argv=None):
     ap.add_argument("--repetition-penalty", type=float, default=1.0, help="1: off; applies to greedy decoding too")
     ap.add_argument("--sample-seed", type=int, default=0, help="seed of the draws (--seed is the question shuffle's); a completion "
                     "depends on it and on the example's index, not on --slots")
+    ap.add_argument("--logprobs", action="store_true", help="add the columns sum_logprob, mean_logprob and n_tokens: log-probabilities of the "
+                    "generated tokens under the model's raw logits (no penalty, temperature, top-k or top-p applied), computed on the device")
     ap.add_argument("--mm_hidden_size", type=int, default=None)
     ap.add_argument("--model_max_length", type=int, default=2048)
     ap.add_argument("--llm-precision", default="split", choices=["split", "bf16"])
@@ -616,7 +746,8 @@ def main_shards(argv=None):
     model, tok, end_seq, mm_cfg = _load_for_inference(args, args.slots)
     recs = infer_from_shards(model, tok, args.eval_data_path, mm_cfg, end_seq, outfile=args.outfile, slots=args.slots,
                              max_samples=args.max_samples, max_new_tokens=args.max_new_tokens, prompt=args.prompt, seed=args.seed,
-                             allow_pickle=args.allow_pickle, share_prefix=args.share_prefix, sampling=sampling if sampling.active else None)
+                             allow_pickle=args.allow_pickle, share_prefix=args.share_prefix, sampling=sampling if sampling.active else None,
+                             **(dict(logprobs=True) if args.logprobs else {}))
     print(f"writing {len(recs)} results to {args.outfile}")
     return recs
 

@@ -26,6 +26,7 @@ from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutpu
 from .. import ops
 from . import AudioEncoderConfig
 from .engine import HipLlamaEngine, LlamaDims
+from .logprob import ragged_logprob_hook, ragged_logprob_matrix
 from .sampling import DeviceSampler, params_from_generate
 from .special_tokens import DEFAULT_AUDIO_END_TOKEN, DEFAULT_AUDIO_PATCH_TOKEN, DEFAULT_AUDIO_START_TOKEN
 
@@ -374,7 +375,8 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
     @torch.no_grad()
     def generate(self, input_ids=None, audio_encodings=None, max_new_tokens: int = 20, do_sample: bool = False,
                  stopping_criteria=None, eos_token_id=None, temperature: float = 1.0, attention_mask=None, top_k: Optional[int] = None,
-                 top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, seed: Optional[int] = None, **kwargs):
+                 top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, seed: Optional[int] = None,
+                 return_logprobs: bool = False, **kwargs):
         """Greedy / temperature sampling loop with the semantics of HF 4.29.2 ``generate`` driven by
         :meth:`prepare_inputs_for_generation`: the full prompt (with audio) once, then one token per step
         against the engine's KV cache; ``stopping_criteria`` are called as ``c(ids, scores)`` each step
@@ -385,11 +387,16 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
         ``do_sample`` with ``temperature`` alone draws with ``torch.multinomial`` from torch's global generator, as ever.  Any of
         ``top_k`` / ``top_p`` / ``repetition_penalty`` / ``seed`` moves the token choice to the device sampler
         (:mod:`llark_amd.m2t.sampling`, HF 4.29.2's processor order; ``top_k`` None or 0: off): draws are Philox under ``seed`` with the
-        batch row as stream id, and ``do_sample=False`` with a ``repetition_penalty`` is penalised greedy search."""
+        batch row as stream id, and ``do_sample=False`` with a ``repetition_penalty`` is penalised greedy search.
+
+        ``return_logprobs``: returns ``(ids, logprobs)``; ``logprobs`` is fp32 ``[B, new tokens]`` on the device, NaN wherever a finished
+        row emitted padding.  They are log-probabilities of the MODEL's distribution -- log-softmax of the raw logits, one
+        ``ops.token_logprob_rows`` launch per step; repetition penalty, temperature, top-k and top-p are not applied, whichever way the
+        token was chosen (greedy, device sampler, ``torch.multinomial``)."""
         sampling = params_from_generate(do_sample, temperature, top_k, top_p, repetition_penalty, seed)
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
             return self._generate_ragged(input_ids, attention_mask, audio_encodings, max_new_tokens, do_sample, stopping_criteria,
-                                         eos_token_id, temperature, sampling)
+                                         eos_token_id, temperature, sampling, return_logprobs)
         ids = input_ids.to(self.engine.device)
         sampler = None
         eos = eos_token_id if eos_token_id is not None else getattr(self.generation_config, "eos_token_id", None)
@@ -397,6 +404,7 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
         pad = eos if pad is None else pad
         unfinished = torch.ones((ids.shape[0], 1), dtype=torch.bool, device=ids.device)      # HF: unfinished_sequences, per row
         past = None
+        lps = []
         for _ in range(max_new_tokens):
             inputs = self.prepare_inputs_for_generation(ids, past_key_values=past, audio_encodings=audio_encodings)
             eng = self.engine
@@ -425,6 +433,9 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
                 nxt = torch.multinomial(probs, 1)
             else:
                 nxt = scores.argmax(-1, keepdim=True)
+            if return_logprobs:                                                               # -1: a finished row has no target
+                lps.append(ops.token_logprob_rows(scores, torch.where(unfinished, nxt, torch.full_like(nxt, -1)).view(-1).contiguous(),
+                                                  torch.full((ids.shape[0],), float("nan"), dtype=torch.float32, device=ids.device)))
             if eos is not None and eos >= 0:
                 nxt = torch.where(unfinished, nxt, torch.full_like(nxt, pad))                 # finished rows emit padding
                 unfinished = unfinished & (nxt != eos)
@@ -433,10 +444,12 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
                 break
             if stopping_criteria is not None and any(bool(c(ids, scores)) for c in stopping_criteria):
                 break
+        if return_logprobs:
+            return ids, (torch.stack(lps, dim=1) if lps else torch.empty((ids.shape[0], 0), dtype=torch.float32, device=ids.device))
         return ids
 
     def _generate_ragged(self, input_ids, attention_mask, audio_encodings, max_new_tokens, do_sample, stopping_criteria, eos_token_id,
-                         temperature, sampling=None):
+                         temperature, sampling=None, return_logprobs=False):
         """generate() over a padded batch: row b is the sequence input_ids[b][mask[b]] at positions 0 .. len_b - 1 (HF's
         position_ids = cumsum(mask) - 1), one engine slot per row (prefill_slots / decode_slots).  Returns the HF layout: the input
         as given followed by the new tokens; rows that finished emit the pad token."""
@@ -450,7 +463,7 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
             raise ValueError("attention_mask selects no token in some row")
         ids_dev = input_ids.to(eng.device)
         if max_new_tokens <= 0:
-            return ids_dev
+            return (ids_dev, torch.empty((B, 0), dtype=torch.float32, device=eng.device)) if return_logprobs else ids_dev
         ids_cpu = input_ids.detach().cpu()
         rows = [ids_cpu[b][am[b]] for b in range(B)]
         packed = torch.zeros((B, int(lens.max())), dtype=torch.int64)               # right-aligned copy for the splice plan
@@ -484,6 +497,10 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
 
             def sample(scores):
                 return sampler(scores, state=eng.slot_state)
+        tracker = None
+        if return_logprobs:
+            tracker, pick = ragged_logprob_hook(eng, B, scores.shape[-1], max_new_tokens, sample if do_sample else None)
+            sample, do_sample = pick, True
         nxt, _ = eng.advance_slots(scores, eos_k, pad_k, out[:, S], sample(scores) if do_sample else None, advance=False)
         n = 1
         while True:
@@ -496,6 +513,8 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
                 break
             nxt, _, scores = eng.decode_slots(nxt, eos_k, pad_k, out[:, S + n], sample if do_sample else None)
             n += 1
+        if tracker is not None:
+            return out[:, : S + n], ragged_logprob_matrix(tracker, n)
         return out[:, : S + n]
 
     def initialize_audio_tokenizer(self, mm_use_audio_start_end, tokenizer, device, tune_mm_mlp_adapter=False,

@@ -27,6 +27,7 @@ from transformers.modeling_outputs import CausalLMOutputWithPast
 from .. import ops
 from . import AudioEncoderConfig
 from .llamav2 import EngineCache, plan_audio_splice
+from .logprob import ragged_logprob_hook, ragged_logprob_matrix
 from .mpt_engine import HipMptEngine, MptDims
 from .sampling import DeviceSampler, params_from_generate
 from .special_tokens import DEFAULT_AUDIO_END_TOKEN, DEFAULT_AUDIO_PATCH_TOKEN, DEFAULT_AUDIO_START_TOKEN
@@ -295,21 +296,28 @@ class WrappedMPTForCausalLM(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids=None, audio_encodings=None, max_new_tokens: int = 20, stopping_criteria=None, eos_token_id=None,
                  attention_mask=None, pad_token_id=None, do_sample: bool = False, temperature: float = 1.0, top_k: Optional[int] = None,
-                 top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, seed: Optional[int] = None, **kwargs):
+                 top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, seed: Optional[int] = None,
+                 return_logprobs: bool = False, **kwargs):
         """Generation loop driven by :meth:`prepare_inputs_for_generation` (prompt with audio once, then one token per step).  An
         ``attention_mask`` with zeros (left- or right-padded) runs every row as if it were alone on the engine's ragged slot mode
         (:meth:`_generate_ragged`); ``None`` or all ones takes this uniform path and never enters the slot mode.
 
         Greedy by default.  ``do_sample`` (with ``temperature``, ``top_k``, ``top_p``, ``repetition_penalty``, ``seed``; ``top_k`` None or
         0: off) chooses every token with the device sampler (:mod:`llark_amd.m2t.sampling`, HF 4.29.2's processor order; Philox draws
-        under ``seed``, the batch row as stream id); ``do_sample=False`` with a ``repetition_penalty`` is penalised greedy search."""
+        under ``seed``, the batch row as stream id); ``do_sample=False`` with a ``repetition_penalty`` is penalised greedy search.
+
+        ``return_logprobs``: returns ``(ids, logprobs)``; ``logprobs`` is fp32 ``[B, new tokens]`` on the device, NaN wherever a finished
+        row emitted padding (the padded path; the uniform path emits none).  They are log-probabilities of the MODEL's distribution --
+        log-softmax of the raw logits, one ``ops.token_logprob_rows`` launch per step; repetition penalty, temperature, top-k and top-p
+        are not applied, for sampled tokens too."""
         sampling = params_from_generate(do_sample, temperature, top_k, top_p, repetition_penalty, seed, always=bool(do_sample))
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
             return self._generate_ragged(input_ids, attention_mask, audio_encodings, max_new_tokens, stopping_criteria, eos_token_id,
-                                         pad_token_id, sampling)
+                                         pad_token_id, sampling, return_logprobs)
         ids = input_ids.to(self.engine.device)
         past = None
         sampler = None
+        lps = []
         for _ in range(max_new_tokens):
             inp = self.prepare_inputs_for_generation(ids, past_key_values=past, audio_encodings=audio_encodings)
             out = self.forward(inp["input_ids"], past_key_values=inp["past_key_values"], audio_encodings=inp["audio_encodings"])
@@ -322,15 +330,20 @@ class WrappedMPTForCausalLM(nn.Module):
                 nxt = sampler(scores).view(-1, 1)
             else:
                 nxt = scores.argmax(-1, keepdim=True)
+            if return_logprobs:
+                lps.append(ops.token_logprob_rows(scores, nxt.view(-1).contiguous(),
+                                                  torch.full((ids.shape[0],), float("nan"), dtype=torch.float32, device=ids.device)))
             ids = torch.cat((ids, nxt), dim=1)
             if eos_token_id is not None and bool((nxt == eos_token_id).all()):
                 break
             if stopping_criteria is not None and any(bool(c(ids, scores)) for c in stopping_criteria):
                 break
+        if return_logprobs:
+            return ids, (torch.stack(lps, dim=1) if lps else torch.empty((ids.shape[0], 0), dtype=torch.float32, device=ids.device))
         return ids
 
     def _generate_ragged(self, input_ids, attention_mask, audio_encodings, max_new_tokens, stopping_criteria, eos_token_id, pad_token_id,
-                         sampling=None):
+                         sampling=None, return_logprobs=False):
         """generate() over a padded batch (``WrappedLlamav2ForCausalLM._generate_ragged``): row b is the sequence
         input_ids[b][mask[b]] at positions 0 .. len_b - 1, one engine slot per row (prefill_slots / decode_slots).  Returns the HF
         layout: the input as given followed by the new tokens; a row that emitted EOS continues with the pad token (EOS when none)."""
@@ -344,7 +357,7 @@ class WrappedMPTForCausalLM(nn.Module):
             raise ValueError("attention_mask selects no token in some row")
         ids_dev = input_ids.to(eng.device)
         if max_new_tokens <= 0:
-            return ids_dev
+            return (ids_dev, torch.empty((B, 0), dtype=torch.float32, device=eng.device)) if return_logprobs else ids_dev
         ids_cpu = input_ids.detach().cpu()
         rows = [ids_cpu[b][am[b]] for b in range(B)]
         packed = torch.zeros((B, int(lens.max())), dtype=torch.int64)               # left-aligned copy for the splice plan
@@ -368,6 +381,9 @@ class WrappedMPTForCausalLM(nn.Module):
 
             def sample(scores):
                 return sampler(scores, state=eng.slot_state)
+        tracker = None
+        if return_logprobs:
+            tracker, sample = ragged_logprob_hook(eng, B, scores.shape[-1], max_new_tokens, sample)
         nxt, _ = eng.advance_slots(scores, eos_k, pad_k, out[:, S], None if sample is None else sample(scores), advance=False)
         n = 1
         while True:
@@ -379,4 +395,6 @@ class WrappedMPTForCausalLM(nn.Module):
                 break
             nxt, _, scores = eng.decode_slots(nxt, eos_k, pad_k, out[:, S + n], sample)
             n += 1
+        if tracker is not None:
+            return out[:, : S + n], ragged_logprob_matrix(tracker, n)
         return out[:, : S + n]

@@ -1162,6 +1162,36 @@ def seen_mark_rows(ids: torch.Tensor, offs: torch.Tensor, lens: torch.Tensor, se
                                           _dev(seen, "seen", i32, contiguous=False), seen.stride(0), _stream()), "seen_mark_rows")
 
 
+def token_logprob_rows(logits: torch.Tensor, tokens: torch.Tensor, logprob: torch.Tensor, *, vocab: Optional[int] = None,
+                       rank: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None,
+                       slot_of_row: Optional[torch.Tensor] = None, hist: Optional[torch.Tensor] = None,
+                       count: Optional[torch.Tensor] = None, total: Optional[torch.Tensor] = None,
+                       slots: Optional[int] = None) -> torch.Tensor:
+    """Log-probability of ``tokens[r]`` (int64 [rows]) under row r of fp32 ``logits`` [rows, >= vocab] into ``logprob`` (fp32 [rows]) in
+    one launch: log-softmax of the RAW logits -- the model's own distribution; no penalty, temperature, top-k or top-p is applied.
+    ``rank`` (int32 [rows]): how many logits are strictly larger (0: a greedy token).  Row r belongs to slot ``slot_of_row[r]`` (identity
+    without it); rows of a slot that is not ROW_ACTIVE (with ``state``, int32 [slots]) and rows whose token is outside [0, vocab) -- a
+    negative token marks "no target" -- are skipped: their outputs keep what they held.  ``hist`` (fp32 [slots, width]) / ``count``
+    (int32 [slots]) / ``total`` (fp32 [slots]) collect each slot's values.  Contract: include/llark_hip.h (llark_token_logprob_rows)."""
+    i32 = torch.int32
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    rows = logits.shape[0]
+    vocab = logits.shape[1] if vocab is None else int(vocab)
+    assert 0 < vocab <= logits.shape[1] and tokens.numel() == rows and logprob.numel() == rows
+    per_slot = [t for t in (state, count, total) if t is not None]
+    if slots is None:
+        slots = hist.shape[0] if hist is not None else per_slot[0].numel() if per_slot else rows
+    assert all(t.numel() == slots for t in per_slot) and (hist is None or (hist.dim() == 2 and hist.shape[0] == slots and hist.stride(1) == 1))
+    assert all(t is None or t.numel() == rows for t in (slot_of_row, rank))
+    check(_lib.lib().llark_token_logprob_rows(_dev(logits, "logits", torch.float32, contiguous=False), logits.stride(0), vocab, rows,
+                                              int(slots), _opt(state, "state", i32), _opt(slot_of_row, "slot_of_row", i32),
+                                              _dev(tokens, "tokens", torch.int64), _dev(logprob, "logprob", torch.float32),
+                                              _opt(rank, "rank", i32), _opt(hist, "hist", torch.float32),
+                                              hist.shape[1] if hist is not None else 0, _opt(count, "count", i32),
+                                              _opt(total, "total", torch.float32), _stream()), "token_logprob_rows")
+    return logprob
+
+
 # ------------------------------------------------------------------------------------------------
 # MPT
 # ------------------------------------------------------------------------------------------------

@@ -27,6 +27,11 @@ Greedy against sampled decode step, same run: every slot active, blocks of 16 st
 whose tokens come from the device sampler (temperature 0.7, top-k 200, top-p 0.95, repetition penalty 1.3; one more launch per step),
 which kind goes first alternating too.  Per slot count: the median block of either kind, the spread of the blocks, and the sampled
 step's excess as a fraction of the greedy step.  ONE JSON line.
+
+    python scripts/bench_generate_inflight.py --logprobs [--slots 16,64] [--out profiles/bench_generate_inflight_logprobs.json]
+Greedy against greedy + token log-probabilities, same run and same block scheme: the second kind's step picks its token with
+ops.sample_rows(do_sample=False) and appends its log-probability to the slot's history (ops.token_logprob_rows), two more launches per
+step, as EngineSlots(logprobs=True) does.  ONE JSON line, also written to --out.
 """
 import argparse
 import json
@@ -303,10 +308,71 @@ def main_sampling(args, slot_list):
     print(json.dumps(res), flush=True)
 
 
+def main_logprobs(args, slot_list):
+    import statistics
+
+    from llark_amd import ops
+    from llark_amd.m2t.logprob import LogprobTracker
+    steps, blocks = 16, 8
+    examples = make_examples(64, args.seed)
+    max_seq = max(ids.numel() for ids, _, _ in examples) + 8 + steps * (2 * blocks + 2)
+    model = RandomLlama(args.precision, max(slot_list), max_seq)
+    eng = model.engine
+    res = {"bench": "generate_inflight_logprobs", "model": "llama2-7b dims, random weights", "precision": args.precision,
+           "steps_per_block": steps, "blocks": blocks, "slots": {}}
+    for n in slot_list:
+        eng.init_slots(n)
+        rows = [examples[i % len(examples)] for i in range(n)]
+        logits = eng.prefill_slots([r[0].cuda() for r in rows], [(k, 1, r[1].cuda()) for k, r in enumerate(rows)], range(n))
+        tracker = LogprobTracker(n, logits.shape[-1], eng.device, eng.smax)
+        choice = torch.zeros((n,), dtype=torch.int64, device=eng.device)
+
+        def with_logprobs(lg):
+            toks = ops.sample_rows(lg, choice, state=eng.slot_state, do_sample=False, repetition_penalty=1.0)
+            tracker(lg, toks, state=eng.slot_state)
+            return toks
+
+        kinds = {"greedy": None, "logprobs": with_logprobs}
+        ids = logits.argmax(-1)
+
+        def block(kind):
+            nonlocal ids
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                ids, _, _ = eng.decode_slots(ids, sample=kinds[kind])
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / steps * 1e3
+
+        block("greedy"), block("logprobs")                       # warm
+        ms = {"greedy": [], "logprobs": []}
+        for b in range(blocks):
+            for kind in (("greedy", "logprobs") if b % 2 == 0 else ("logprobs", "greedy")):
+                ms[kind].append(block(kind))
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        taken = tracker.take(range(n))
+        assert all(h.numel() == steps * (blocks + 1) and bool(torch.isfinite(h).all()) for h in taken)
+        cell = {"greedy_step_ms": round(med["greedy"], 4), "logprobs_step_ms": round(med["logprobs"], 4),
+                "greedy_min_max_ms": [round(min(ms["greedy"]), 4), round(max(ms["greedy"]), 4)],
+                "logprobs_min_max_ms": [round(min(ms["logprobs"]), 4), round(max(ms["logprobs"]), 4)],
+                "excess_fraction_of_step": round(med["logprobs"] / med["greedy"] - 1.0, 4)}
+        res["slots"][str(n)] = cell
+        print(json.dumps({str(n): cell}), file=sys.stderr, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--sampling", action="store_true", help="same-run A/B of the decode step with every slot active: greedy against the "
                     "device sampler (default slot counts 16,64)")
+    ap.add_argument("--logprobs", action="store_true", help="same-run A/B of the decode step with every slot active: greedy against greedy + "
+                    "token log-probabilities (default slot counts 16,64)")
+    ap.add_argument("--out", default=None, help="with --logprobs: also write the JSON here (default profiles/bench_generate_inflight_logprobs.json)")
     ap.add_argument("--questions-per-clip", default=None, help="e.g. 1,4,8: consecutive examples share an encoding, an audio-first prefix "
                     "and a prefix key (inflight schedule only; one result cell per slot count and value)")
     ap.add_argument("--share-prefix", action="store_true", help="with --questions-per-clip: run every cell with share_prefix off and on")
@@ -323,6 +389,10 @@ def main():
         ap.error(f"--slots takes counts in 1 .. 64, got {args.slots!r}")
     if args.sampling:
         return main_sampling(args, [16, 64] if args.slots == ap.get_default("slots") else slot_list)
+    if args.logprobs:
+        if args.out is None:
+            args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "bench_generate_inflight_logprobs.json")
+        return main_logprobs(args, [16, 64] if args.slots == ap.get_default("slots") else slot_list)
     if args.questions_per_clip:
         return main_shared(args, slot_list)
     if args.share_prefix:
