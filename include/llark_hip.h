@@ -609,6 +609,60 @@ int llark_seen_mark_rows(const int64_t* ids, long long n_ids, const int* offs, c
 int llark_token_logprob_rows(const float* logits, int ldl, int vocab, int rows, int slots, const int* state, const int* slot_of_row,
                              const int64_t* tokens, float* logprob, int* rank, float* hist, int ld_hist, int* count, float* total,
                              llark_stream_t stream);
+/* Beam search on the device (csrc/beam.hip): the step of HF 4.29.2's beam_search + BeamSearchScorer with one beam group, after the logits.
+ * Example e of n_examples owns the `beams` (B, 1 .. 16) consecutive slots e * B .. e * B + B - 1; a beam's RANK (its place in HF's order) and
+ * its SLOT are different things: rank_of_slot int32 [slots].
+ *   llark_beam_topk_rows: one workgroup per row r of logits fp32 [rows][ldl]; slot_of_row, state and the skip rules are those of
+ *     llark_token_logprob_rows (a skipped row: nothing read, nothing written).  With lp(t) = (l_t - M) - logf(S) -- M, S and therefore lp
+ *     bit-equal to llark_token_logprob_rows for that row and token (same column ownership, same summation order) -- and cand(t) =
+ *     fp32(score[slot] + lp(t)) (score fp32 [slots]), the 2B largest candidates of the row, ordered by cand descending, then t ascending:
+ *       cand_score fp32 [rows][2B], cand_token int32 [rows][2B], cand_logprob fp32 [rows][2B] (= lp of that token).
+ *     A row that holds a NaN, or whose maximum is +-inf: all 2B entries are (-inf, -1, -inf) and *fallbacks (nullable) += 1.  Any vocab; a
+ *     row of up to 51 200 columns is read from memory once.  Bit-reproducible: depends on the row's floats and the score alone.
+ *     LLARK_ERR_INVALID before any launch: a null logits / score / cand_*, beams outside 1 .. 16, vocab < 2B, ldl < vocab, rows or slots
+ *     <= 0, rows > slots without slot_of_row.
+ *   llark_beam_advance: one workgroup per example, from the B * 2B candidates of its slots (cand_* indexed [slot][2B]: row = slot); a merge
+ *     of sorted lists, no second pass over the vocabulary.  An example with done[e] != 0 only gets next_ids = pad, an empty trellis row
+ *     (-1, -1, NaN) and pair_count[e] = 0.  Otherwise, with cur_len[e] the length, prompt included, before the new token:
+ *       the top 2B of the example's candidates are walked in the order cand descending, rank ascending, token ascending; k = place in
+ *       that order.  token == eos (eos >= 0): k >= B skipped, k < B a hypothesis (sum = cand, length = cur_len, end step = step, end slot =
+ *       the beam's global slot: its tokens are that beam's, without the eos).  A token of -1 is never taken.  Anything else becomes the live
+ *       beam of the next free rank; the walk ends with the B-th.
+ *       Adding a hypothesis: score = fp32(sum / length^length_penalty) (the quotient in double); kept when the heap holds fewer than B or
+ *       score > worst, replacing the lowest score (the earliest arrival among equals).
+ *       done[e] |= heap full and (early_stopping or worst >= fp32(cand of k = 0 / cur_len^length_penalty)); also when fewer than B live
+ *       beams were found.  A done example's slots become LLARK_ROW_FINISHED and emit pad, from this step on.
+ *       Slots: the first accepted child of a parent stays in the parent's slot; every further child takes, in rank order, the lowest slot
+ *       whose old beam has no child this step, and (src = parent's slot, dst = that slot) is appended to the example's copy list: every
+ *       copy reads a slot that is not written this step and writes a slot that nobody reads.
+ *     Written: score, rank_of_slot, next_ids int64 [slots] (token of the beam now in that slot), state, pos_rows[slot] += 1 for the B slots
+ *       (pos_rows nullable: the step on the prefill logits advances nothing), cur_len[e] += 1, done[e],
+ *       trellis int32 [max_steps][slots][3]: row `step`, entry of a slot = (parent's global slot, token, bits of the token's fp32 lp); rows are
+ *         never rewritten, a hypothesis' tokens are found by walking parents from (end step - 1, end slot);
+ *       heap int32 [n_examples][B][8] = {score f32, sum f32, length, end step, end slot, order of arrival, lp of the closing eos f32, 0},
+ *       heap_meta int32 [n_examples][4] = {count, worst score f32 (caller: 1e9 while empty), arrivals, 0};
+ *       pairs int32 [n_examples][max(B - 1, 1)][2] = (src, dst) global slots, pair_count int32 [n_examples].
+ *     LLARK_ERR_INVALID before any launch: a null pointer other than pos_rows, beams outside 1 .. 16, n_examples outside 1 .. 4096, step
+ *     outside [0, max_steps), a length_penalty that is not finite.
+ *   llark_kv_copy_slots: for entry i < count[l] of list l of a copy table in DEVICE memory (pairs int32 [n_lists][list_stride][2], count int32
+ *     [n_lists]; one list with its count is n_lists = 1): positions [p0[dst], pos_rows[src]) of cache slot src into slot dst, every layer,
+ *     the lo planes too when given (both or none).  p0 int32 [slots] holds multiples of 8; layout, 16-byte chunks and the rule for V^T rows
+ *     (positions up to round_up(pos_rows[src], 8) - 1 of dst are overwritten, nothing else) are those of llark_kv_copy_prefix.  The grid is
+ *     sized from max_span, the caller's upper bound on pos_rows[src] - p0[dst].  Nothing is copied for an entry at or past its count, with a
+ *     slot outside [0, slots), with src == dst, with a p0 that is negative or no multiple of 8, an empty span, pos_rows[src] > smax or a
+ *     span above max_span.  LLARK_ERR_INVALID before any launch: a null pointer or one lo plane only, hd != 128, smax % 8 != 0, layers *
+ *     nh > 65535, n_lists * list_stride outside 1 .. 1024, max_span outside 1 .. smax.
+ *   No workgroup waits for another; the only atomic is the add on *fallbacks. */
+int llark_beam_topk_rows(const float* logits, int ldl, int vocab, int rows, int slots, const int* state, const int* slot_of_row,
+                         const float* score, int beams, float* cand_score, int* cand_token, float* cand_logprob, int* fallbacks,
+                         llark_stream_t stream);
+int llark_beam_advance(const float* cand_score, const int* cand_token, const float* cand_logprob, int n_examples, int beams, int step,
+                       int max_steps, int64_t eos, int64_t pad, float length_penalty, int early_stopping, float* score, int* rank_of_slot,
+                       int* state, int* pos_rows, int* cur_len, int64_t* next_ids, int* heap, int* heap_meta, int* done, int* trellis,
+                       int* pairs, int* pair_count, llark_stream_t stream);
+int llark_kv_copy_slots(void* k_cache, void* vt_cache, void* k_cache_lo, void* vt_cache_lo, int layers, int slots, int nh, int hd, int smax,
+                        const int* pairs, const int* count, int n_lists, int list_stride, const int* p0, const int* pos_rows, int max_span,
+                        llark_stream_t stream);
 /* MPT ragged decode step, the whole attention front in one launch (m2t/llava/model/mpt/attention.py: qkv.clamp_ -> q_ln / k_ln ->
  * head split -> attention with the ALiBi bias; replaces llark_clamp_f32 + 2 x llark_layernorm_f32 + llark_attn_decode_rope_bf16_rows
  * with identity tables).  qkv fp32 [batch][ldq], laid out q | k | v with nh*128 columns each, is READ ONLY.  Workgroup (h, b) reads

@@ -809,6 +809,28 @@ class HipLlamaEngine:
             self.slot_lineage[b], self.slot_shared_host[b] = self.slot_lineage[src], min(n, self.slot_shared_host[src])
             self._forked[b], self.slot_len_host[b] = n, n
 
+    def clone_slots(self, src: int, dsts: Sequence[int]) -> None:
+        """Copy the whole of the active slot `src` into the idle slots `dsts` (every layer and plane, one launch): they become active
+        at the same length and join src's lineage (a new one if src had none), so with share_prefix the group attention reads what they
+        have in common once.  The beams of one example start this way: the prompt is prefilled once."""
+        src, dsts = self._check_slots([src])[0], self._check_slots(dsts)
+        if self.slot_state_host[src] != ops.ROW_ACTIVE or src in self._forked:
+            raise ValueError(f"clone_slots: source slot {src} is not active")
+        busy = [b for b in dsts if self.slot_len_host[b] >= 0 or b in self._forked]
+        if busy or src in dsts:
+            raise ValueError(f"clone_slots: destination slots {busy or [src]} are not idle")
+        if not dsts:
+            return
+        n = self.slot_len_host[src]
+        ops.kv_copy_prefix(self.k_cache, self.vt_cache, src, dsts, n, self.k_cache_lo, self.vt_cache_lo)
+        if self.slot_lineage[src] is None:
+            self.slot_lineage[src], self.slot_shared_host[src] = self._lineages, self.smax
+            self._lineages += 1
+        for b in dsts:
+            self.slot_lineage[b], self.slot_shared_host[b] = self.slot_lineage[src], min(n, self.slot_shared_host[src])
+        self._set_slots(dsts, [n] * len(dsts), ops.ROW_ACTIVE)
+        self._rebuild_groups()
+
     def _rebuild_groups(self) -> None:
         """The decode step's group table, from the host's view of the slots: the non-idle slots of one lineage (forked ones only once
         their suffix is in) form a group; its shared length is the smallest of its members', rounded down to a multiple of 8 (the
@@ -977,6 +999,12 @@ class HipLlamaEngine:
         token of each slot at position slot_len; idle rows pass through the row-independent GEMMs harmlessly).  sample: optional
         callable logits -> int64 [n_slots] tokens (sampling); greedy otherwise.  Returns (next ids on the device, their host copy,
         the step's fp32 logits [n_slots, V] -- a buffer the next step overwrites)."""
+        logits = self._slot_logits(ids)
+        nxt, host = self.advance_slots(logits, eos, pad, out_col, None if sample is None else sample(logits))
+        return nxt, host, logits
+
+    def _slot_logits(self, ids: torch.Tensor) -> torch.Tensor:
+        """The decode step up to the logits: embedding -> decoder layers -> final norm + lm_head, every slot at its own position."""
         n = self.n_slots
         if n == 0:
             raise RuntimeError("ragged mode is not active: call init_slots(n) first")
@@ -990,5 +1018,25 @@ class HipLlamaEngine:
         ops.embed_gather(ids.contiguous(), self.embed, h)
         normed = self._layers_forward(ws, n, 1, 0, pos_rows=self.slot_len)
         self._head(ws, logits, normed, may_fuse=True)
-        nxt, host = self.advance_slots(logits, eos, pad, out_col, None if sample is None else sample(logits))
-        return nxt, host, logits
+        return logits
+
+    def beam_step(self, ids: Optional[torch.Tensor], beam, logits: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, List[bool]]:
+        """One beam-search step over all n_slots rows (beam: llark_amd.m2t.beam.BeamSearch, which owns example e's slots e * B ..):
+        the decode step up to the logits on `ids` (int64 [n_slots], the token of the beam now in each slot), then the three launches
+        of the beam step -- ops.beam_topk_rows, ops.beam_advance, ops.kv_copy_slots -- instead of advance_slots.  ids None: the step on
+        `logits` [n_slots, V] of the prompts' last tokens (replicated per beam): no forward, no position advances and, the slots being
+        clones, no K/V move.  Returns (next ids on the device, the examples' done flags -- the step's one device-to-host transfer)."""
+        first = ids is None
+        if not first:
+            logits = self._slot_logits(ids)
+        B = beam.beams
+        was_done = list(beam.done_host)
+        kv = None if first else (self.k_cache, self.vt_cache, self.k_cache_lo, self.vt_cache_lo)
+        nxt, done = beam.step(logits, self.slot_state, None if first else self.slot_len, kv)
+        for e, (w, dn) in enumerate(zip(was_done, done)):
+            for b in range(e * B, e * B + B):
+                if not w and not first:
+                    self.slot_len_host[b] += 1
+                if dn:
+                    self.slot_state_host[b] = ops.ROW_FINISHED
+        return nxt, done

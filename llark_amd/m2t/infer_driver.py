@@ -84,6 +84,29 @@ def generate_batch(model, input_ids: torch.Tensor, encodings: torch.Tensor, toke
     return [out[b, : (done_at[b] if done_at[b] is not None else out.shape[1])] for b in range(B)]
 
 
+@torch.no_grad()
+def generate_beam(model, input_ids: torch.Tensor, encodings: torch.Tensor, tokenizer, max_new_tokens: int = 512, num_beams: int = 4,
+                  length_penalty: float = 1.0, keywords: Sequence[str] = ("###",)) -> List[torch.Tensor]:
+    """Beam search, one example per ``model.generate(num_beams=...)`` call under the keyword stopping criterion (HF's criterion sees
+    the best live beam first, as the reference's loop would).  Returns, per example, prompt + the best hypothesis' ids: the eos that
+    generate puts behind a short row, and the padding, are cut."""
+    eos = getattr(getattr(model, "generation_config", None), "eos_token_id", None)
+    S, outs = input_ids.shape[1], []
+    for b in range(input_ids.shape[0]):
+        stop = KeywordsStoppingCriteria(keywords=list(keywords), tokenizer=tokenizer, input_ids=input_ids[b: b + 1])
+        row = model.generate(input_ids=input_ids[b: b + 1], audio_encodings=encodings[b: b + 1], max_new_tokens=max_new_tokens,
+                             stopping_criteria=[stop], num_beams=num_beams, length_penalty=length_penalty)[0].cpu()
+        hit = (row[S:] == eos).nonzero() if eos is not None and eos >= 0 else torch.empty((0, 1))
+        outs.append(row[: S + int(hit[0])] if hit.numel() else row)
+    return outs
+
+
+def refuse_beams(where: str, num_beams) -> None:
+    """Beam search runs through WrappedLlamav2ForCausalLM.generate only: everywhere else the argument is refused, not ignored."""
+    if num_beams is not None and num_beams != 1:
+        raise NotImplementedError(f"{where}: num_beams={num_beams!r} is not implemented here (beam search: WrappedLlamav2ForCausalLM.generate)")
+
+
 MIN_SHARED = 64      # fewest common leading tokens worth a fork; the engine's own (untuned) default, HipLlamaEngine.MIN_SHARED
 
 
@@ -341,7 +364,8 @@ class EngineSlots:
 @torch.no_grad()
 def generate_inflight(model, examples: Iterable[Sequence[Any]], slots: int = 8, max_new_tokens: int = 512,
                       keywords: Sequence[str] = ("###",), tokenizer=None, trace: Optional[list] = None,
-                      share_prefix: bool = False, sampling=None, return_logprobs: bool = False) -> Iterator[Tuple[int, torch.Tensor]]:
+                      share_prefix: bool = False, sampling=None, return_logprobs: bool = False,
+                      num_beams: Optional[int] = None) -> Iterator[Tuple[int, torch.Tensor]]:
     """Generation (greedy unless ``sampling``) with in-flight slot refill.  ``examples`` yields ``(prompt_ids, encoding[, max_new_tokens[, prefix_key]])`` with prompts
     of any length; up to ``slots`` of them decode together, each at its own KV-cache length, and a finished row's slot is refilled
     from the iterable (contiguous free slots prefilled as one batch) while the others keep decoding.  Stops per row as in
@@ -357,6 +381,7 @@ def generate_inflight(model, examples: Iterable[Sequence[Any]], slots: int = 8, 
     included.  They are log-probabilities of the MODEL's distribution: log-softmax of the raw logits, computed on the device in the
     step's own launch sequence (``llark_token_logprob_rows``); repetition penalty, temperature, top-k and top-p are not applied, for
     sampled tokens too.  Refused with a model's own ``slot_backend`` as sampling is."""
+    refuse_beams("generate_inflight", num_beams)
     if keywords and tokenizer is None:
         raise ValueError("generate_inflight: keyword stopping needs the tokenizer")
     make = getattr(model, "slot_backend", None)
@@ -468,10 +493,10 @@ def _write_csv(records: List[Dict[str, str]], outfile: Optional[str]) -> None:
 def infer_from_encodings(model, tokenizer, audio_encodings_dir: str, prompt: str, multimodal_cfg: Dict[str, Any],
                          end_seq: Sequence[int], outfile: Optional[str] = None, batch_size: int = 8,
                          max_samples: Optional[int] = None, max_new_tokens: int = 512, audio_first: bool = True,
-                         embed_dim: Optional[int] = None) -> List[Dict[str, str]]:
+                         embed_dim: Optional[int] = None, num_beams: int = 1, length_penalty: float = 1.0) -> List[Dict[str, str]]:
     """Directory of ``*.npy`` -> CSV, like ``scripts/inference/infer_from_encodings.py:main`` (same record fields; files
     in sorted order; ``example_id`` = path without ``.npy``).  Examples are grouped by frame count so that every batch
-    shares one prompt length."""
+    shares one prompt length.  ``num_beams`` > 1: beam search with ``length_penalty``, one example per call (:func:`generate_beam`)."""
     if embed_dim is None:                                  # 4800 for Jukebox, 512 for CLAP (ModelArguments.mm_hidden_size)
         embed_dim = int(getattr(getattr(model, "config", None), "mm_hidden_size", EMBED_DIM))
     paths = sorted(glob.glob(os.path.join(audio_encodings_dir, "*.npy")))
@@ -488,7 +513,10 @@ def infer_from_encodings(model, tokenizer, audio_encodings_dir: str, prompt: str
             chunk = items[i: i + batch_size]
             enc = torch.from_numpy(np.stack([a for _, a in chunk])).cuda()
             ids = prompt_ids.unsqueeze(0).repeat(len(chunk), 1)
-            outs = generate_batch(model, ids, enc, tokenizer, max_new_tokens)
+            if num_beams is not None and num_beams != 1:
+                outs = generate_beam(model, ids, enc, tokenizer, max_new_tokens, num_beams, length_penalty)
+            else:
+                outs = generate_batch(model, ids, enc, tokenizer, max_new_tokens)
             for rec in _rows_to_records([p[: -len(".npy")] for p, _ in chunk], prompt, outs, end_seq, tokenizer):
                 records[rec["example_id"]] = rec
     ordered = [records[p[: -len(".npy")]] for p in paths]
@@ -555,7 +583,8 @@ LOGPROB_COLUMNS = ["sum_logprob", "mean_logprob", "n_tokens"]
 def infer_from_shards(model, tokenizer, shards: str, multimodal_cfg: Dict[str, Any], end_seq: Sequence[int], outfile: Optional[str] = None,
                       slots: int = 8, max_samples: Optional[int] = None, max_new_tokens: int = 512, prompt: Optional[str] = None,
                       seed: int = 0, allow_pickle: bool = False, header: str = DEFAULT_CONVERSATION_HEADER,
-                      share_prefix: bool = False, sampling=None, logprobs: bool = False) -> List[Dict[str, str]]:
+                      share_prefix: bool = False, sampling=None, logprobs: bool = False,
+                      num_beams: Optional[int] = None) -> List[Dict[str, str]]:
     """Local tar shards -> CSV under the contract of ``scripts/inference/infer_from_webdataset.py:51-151``: every (question,
     answer) pair of a sample is one example whose prompt is its own human turn up to "### Assistant:" (audio placeholder first
     or last by a draw seeded with ``seed``); ``prompt`` overrides every question (the reference's ``--prompt``: audio first).
@@ -569,6 +598,7 @@ def infer_from_shards(model, tokenizer, shards: str, multimodal_cfg: Dict[str, A
     logits; repetition penalty, temperature, top-k and top-p are not applied, for sampled tokens too."""
     from .data import element_to_conversations, expand_urls, iter_tar_samples
 
+    refuse_beams("infer_from_shards", num_beams)
     rng = random.Random(seed)
     meta: List[Dict[str, str]] = []
 
@@ -639,12 +669,15 @@ def main(argv=None):
     ap.add_argument("--mm_hidden_size", type=int, default=None)
     ap.add_argument("--model_max_length", type=int, default=2048)
     ap.add_argument("--llm-precision", default="split", choices=["split", "bf16"])
+    ap.add_argument("--num_beams", type=int, default=1, help="beam search with this many beams (1 .. 16), one example per call; 1: greedy")
+    ap.add_argument("--length_penalty", type=float, default=1.0, help="hypothesis score = sum of log-probabilities / length ** this")
     for ignored in ("--ckpt-num", "--report_to", "--bf16", "--tf32", "--output_dir"):
         ap.add_argument(ignored, default=None, help="accepted for script compatibility")
     args = ap.parse_args(argv)
-    model, tok, end_seq, mm_cfg = _load_for_inference(args, args.batch_size)
+    model, tok, end_seq, mm_cfg = _load_for_inference(args, max(args.batch_size, args.num_beams))
     recs = infer_from_encodings(model, tok, args.audio_encodings_dir, args.prompt, mm_cfg, end_seq, outfile=args.outfile,
-                                batch_size=args.batch_size, max_samples=args.max_samples, max_new_tokens=args.max_new_tokens)
+                                batch_size=args.batch_size, max_samples=args.max_samples, max_new_tokens=args.max_new_tokens,
+                                num_beams=args.num_beams, length_penalty=args.length_penalty)
     print(f"writing {len(recs)} results to {args.outfile}")
     return recs
 
@@ -722,6 +755,7 @@ def main_shards(argv=None):
     ap.add_argument("--repetition-penalty", type=float, default=1.0, help="1: off; applies to greedy decoding too")
     ap.add_argument("--sample-seed", type=int, default=0, help="seed of the draws (--seed is the question shuffle's); a completion "
                     "depends on it and on the example's index, not on --slots")
+    ap.add_argument("--num_beams", type=int, default=1, help="refused above 1: beam search is not scheduled in flight")
     ap.add_argument("--logprobs", action="store_true", help="add the columns sum_logprob, mean_logprob and n_tokens: log-probabilities of the "
                     "generated tokens under the model's raw logits (no penalty, temperature, top-k or top-p applied), computed on the device")
     ap.add_argument("--mm_hidden_size", type=int, default=None)
@@ -739,6 +773,7 @@ def main_shards(argv=None):
         ap.error(str(e))
     if not 1 <= args.slots <= 64:
         ap.error(f"--slots must be in 1 .. 64, got {args.slots}")
+    refuse_beams("shards", args.num_beams)
     from .train import backbone_of
 
     if args.share_prefix and backbone_of(args.model_name_or_path) == "mpt":

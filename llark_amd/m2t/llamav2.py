@@ -25,6 +25,7 @@ from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutpu
 
 from .. import ops
 from . import AudioEncoderConfig
+from .beam import BeamSearch, check_beam_args
 from .engine import HipLlamaEngine, LlamaDims
 from .logprob import ragged_logprob_hook, ragged_logprob_matrix
 from .sampling import DeviceSampler, params_from_generate
@@ -376,7 +377,9 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
     def generate(self, input_ids=None, audio_encodings=None, max_new_tokens: int = 20, do_sample: bool = False,
                  stopping_criteria=None, eos_token_id=None, temperature: float = 1.0, attention_mask=None, top_k: Optional[int] = None,
                  top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, seed: Optional[int] = None,
-                 return_logprobs: bool = False, **kwargs):
+                 return_logprobs: bool = False, num_beams: Optional[int] = None, length_penalty: float = 1.0,
+                 early_stopping: bool = False, num_return_sequences: Optional[int] = None, num_beam_groups: Optional[int] = None,
+                 share_prefix: bool = False, **kwargs):
         """Greedy / temperature sampling loop with the semantics of HF 4.29.2 ``generate`` driven by
         :meth:`prepare_inputs_for_generation`: the full prompt (with audio) once, then one token per step
         against the engine's KV cache; ``stopping_criteria`` are called as ``c(ids, scores)`` each step
@@ -392,7 +395,22 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
         ``return_logprobs``: returns ``(ids, logprobs)``; ``logprobs`` is fp32 ``[B, new tokens]`` on the device, NaN wherever a finished
         row emitted padding.  They are log-probabilities of the MODEL's distribution -- log-softmax of the raw logits, one
         ``ops.token_logprob_rows`` launch per step; repetition penalty, temperature, top-k and top-p are not applied, whichever way the
-        token was chosen (greedy, device sampler, ``torch.multinomial``)."""
+        token was chosen (greedy, device sampler, ``torch.multinomial``).
+
+        ``num_beams`` > 1: beam search on the device (:mod:`llark_amd.m2t.beam`, HF 4.29.2's ``beam_search`` with one beam group) with
+        ``length_penalty``, ``early_stopping`` and ``num_return_sequences`` (rows ``[B * num_return_sequences, width]``, best first);
+        uniform and padded batches both run on the slot mode, B * num_beams <= 64 slots.  ``return_logprobs`` then gives the returned
+        rows' per-token values.  ``share_prefix``: the beams of an example read their prompt once per decode step (off by default).
+        Sampling, a repetition penalty and beam groups are refused under beams.  ``num_beams`` 1 or None: the paths above, unchanged."""
+        if num_beam_groups is not None and num_beam_groups != 1:
+            raise NotImplementedError(f"num_beam_groups={num_beam_groups!r}: diverse beam groups are not implemented")
+        if num_beams is not None and num_beams != 1:
+            if do_sample:
+                raise NotImplementedError("do_sample=True with num_beams > 1 (beam sampling) is not implemented")
+            if repetition_penalty is not None and repetition_penalty != 1.0:
+                raise NotImplementedError("repetition_penalty with num_beams > 1 is not implemented (no logits processors under beams)")
+            return self._generate_beam(input_ids, attention_mask, audio_encodings, max_new_tokens, stopping_criteria, eos_token_id,
+                                       num_beams, length_penalty, early_stopping, num_return_sequences, return_logprobs, share_prefix)
         sampling = params_from_generate(do_sample, temperature, top_k, top_p, repetition_penalty, seed)
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
             return self._generate_ragged(input_ids, attention_mask, audio_encodings, max_new_tokens, do_sample, stopping_criteria,
@@ -516,6 +534,66 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
         if tracker is not None:
             return out[:, : S + n], ragged_logprob_matrix(tracker, n)
         return out[:, : S + n]
+
+    def _generate_beam(self, input_ids, attention_mask, audio_encodings, max_new_tokens, stopping_criteria, eos_token_id, num_beams,
+                       length_penalty, early_stopping, num_return_sequences, return_logprobs, share_prefix):
+        """generate(num_beams > 1): example b is the sequence input_ids[b][mask[b]] (all of it without a mask), prefilled once into
+        slot b * num_beams and cloned into the example's other slots; then one engine.beam_step per token.  Returns HF's layout."""
+        eng = self.engine
+        N, S = input_ids.shape
+        B, R, lp = check_beam_args(num_beams, num_return_sequences, length_penalty, N)
+        am = torch.ones((N, S), dtype=torch.bool) if attention_mask is None else attention_mask.to(device="cpu", dtype=torch.bool)
+        if am.shape != (N, S):
+            raise ValueError(f"attention_mask shape {tuple(am.shape)} does not match input_ids {(N, S)}")
+        lens = am.sum(1)
+        if bool((lens == 0).any()):
+            raise ValueError("attention_mask selects no token in some row")
+        if max_new_tokens <= 0:
+            raise ValueError(f"beam search needs max_new_tokens >= 1, got {max_new_tokens}")
+        ids_cpu = input_ids.detach().cpu()
+        rows = [ids_cpu[b][am[b]] for b in range(N)]
+        packed = torch.zeros((N, int(lens.max())), dtype=torch.int64)
+        for b, r in enumerate(rows):
+            packed[b, : r.numel()] = r
+        segs = []
+        if audio_encodings is not None:
+            feats = audio_encodings
+            if isinstance(feats, (list, tuple)):
+                feats = [f.to(device=eng.device, dtype=torch.float32) for f in feats]
+            else:
+                feats = feats.to(device=eng.device, dtype=torch.float32)
+            segs = plan_audio_splice(packed, feats, self.model.audio_encoder_config, False)
+        eos = eos_token_id if eos_token_id is not None else getattr(self.generation_config, "eos_token_id", None)
+        pad = getattr(self.generation_config, "pad_token_id", None)
+        pad = eos if pad is None else pad
+        eng.init_slots(N * B, share_prefix=share_prefix)
+        scores = eng.prefill_slots([r.to(eng.device) for r in rows], segs, [b * B for b in range(N)])
+        for b in range(N):
+            eng.clone_slots(b * B, range(b * B + 1, b * B + B))
+        use_eos = eos is not None and eos >= 0
+        pad_k = int(pad) if use_eos and pad is not None and pad >= 0 else 0       # the pad token is fed to the embedding: a valid id
+        beam = BeamSearch(N, B, scores.shape[-1], max_new_tokens, eng.device, eos if use_eos else None, pad_k, lp, early_stopping)
+        beam.admit([int(n) for n in lens])
+        if getattr(self, "beam_observer", None) is not None:                       # tests: install the BeamSearch hooks before the first step
+            self.beam_observer(beam, eng)
+        scores = scores.repeat_interleave(B, dim=0)
+        cur = input_ids.to(eng.device).repeat_interleave(B, dim=0) if stopping_criteria is not None else None
+        nxt, done = eng.beam_step(None, beam, logits=scores)
+        n = 1
+        while True:
+            if all(done):
+                break
+            if cur is not None:
+                cur = beam.extend_ids(cur)
+                if any(bool(c(beam.by_rank(cur), beam.by_rank(scores))) for c in stopping_criteria):
+                    break
+            if n == max_new_tokens:
+                break
+            nxt, done = eng.beam_step(nxt, beam)
+            scores = eng._slot_ws["logits"]
+            n += 1
+        ids, lps, _ = beam.finalize(input_ids, max_new_tokens, R)
+        return (ids, lps) if return_logprobs else ids
 
     def initialize_audio_tokenizer(self, mm_use_audio_start_end, tokenizer, device, tune_mm_mlp_adapter=False,
                                    pretrain_mm_mlp_adapter=None):

@@ -297,7 +297,7 @@ class WrappedMPTForCausalLM(nn.Module):
     def generate(self, input_ids=None, audio_encodings=None, max_new_tokens: int = 20, stopping_criteria=None, eos_token_id=None,
                  attention_mask=None, pad_token_id=None, do_sample: bool = False, temperature: float = 1.0, top_k: Optional[int] = None,
                  top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, seed: Optional[int] = None,
-                 return_logprobs: bool = False, **kwargs):
+                 return_logprobs: bool = False, num_beams: Optional[int] = None, **kwargs):
         """Generation loop driven by :meth:`prepare_inputs_for_generation` (prompt with audio once, then one token per step).  An
         ``attention_mask`` with zeros (left- or right-padded) runs every row as if it were alone on the engine's ragged slot mode
         (:meth:`_generate_ragged`); ``None`` or all ones takes this uniform path and never enters the slot mode.
@@ -309,7 +309,9 @@ class WrappedMPTForCausalLM(nn.Module):
         ``return_logprobs``: returns ``(ids, logprobs)``; ``logprobs`` is fp32 ``[B, new tokens]`` on the device, NaN wherever a finished
         row emitted padding (the padded path; the uniform path emits none).  They are log-probabilities of the MODEL's distribution --
         log-softmax of the raw logits, one ``ops.token_logprob_rows`` launch per step; repetition penalty, temperature, top-k and top-p
-        are not applied, for sampled tokens too."""
+        are not applied, for sampled tokens too.  ``num_beams`` > 1 is refused: beam search exists on the Llama engine only."""
+        if num_beams is not None and num_beams != 1:
+            raise NotImplementedError(f"num_beams={num_beams!r}: beam search is not implemented for MPT (no K/V fork path there yet)")
         sampling = params_from_generate(do_sample, temperature, top_k, top_p, repetition_penalty, seed, always=bool(do_sample))
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
             return self._generate_ragged(input_ids, attention_mask, audio_encodings, max_new_tokens, stopping_criteria, eos_token_id,

@@ -1192,6 +1192,73 @@ def token_logprob_rows(logits: torch.Tensor, tokens: torch.Tensor, logprob: torc
     return logprob
 
 
+BEAM_MAX = 16                         # beams per example (csrc/beam.hip)
+BEAM_HEAP_STRIDE = 8                  # int32 per heap entry: score f32, sum f32, length, end step, end slot, arrival, eos lp f32, 0
+BEAM_META_STRIDE = 4                  # int32 per example: count, worst score f32, arrivals, 0
+
+
+def beam_topk_rows(logits: torch.Tensor, score: torch.Tensor, beams: int, cand_score: torch.Tensor, cand_token: torch.Tensor,
+                   cand_logprob: torch.Tensor, *, vocab: Optional[int] = None, state: Optional[torch.Tensor] = None,
+                   slot_of_row: Optional[torch.Tensor] = None, fallbacks: Optional[torch.Tensor] = None) -> None:
+    """The 2 * ``beams`` best candidates ``fp32(score[slot] + log_softmax(row)[t])`` of every row of fp32 ``logits`` [rows, >= vocab], sorted
+    by candidate descending, then token ascending, into ``cand_score`` / ``cand_token`` (int32) / ``cand_logprob`` [rows, 2 * beams]; the
+    log-probabilities are bit-equal to :func:`token_logprob_rows`.  ``score`` fp32 [slots]; rows of slots that are not ROW_ACTIVE (with
+    ``state``) are skipped.  Contract: include/llark_hip.h (llark_beam_topk_rows)."""
+    i32, f32 = torch.int32, torch.float32
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    rows = logits.shape[0]
+    vocab = logits.shape[1] if vocab is None else int(vocab)
+    slots = score.numel()
+    assert 0 < vocab <= logits.shape[1] and (state is None or state.numel() == slots) and (slot_of_row is None or slot_of_row.numel() == rows)
+    assert all(t.numel() == rows * 2 * beams for t in (cand_score, cand_token, cand_logprob))
+    check(_lib.lib().llark_beam_topk_rows(_dev(logits, "logits", f32, contiguous=False), logits.stride(0), vocab, rows, slots,
+                                          _opt(state, "state", i32), _opt(slot_of_row, "slot_of_row", i32), _dev(score, "score", f32),
+                                          int(beams), _dev(cand_score, "cand_score", f32), _dev(cand_token, "cand_token", i32),
+                                          _dev(cand_logprob, "cand_logprob", f32), _opt(fallbacks, "fallbacks", i32), _stream()), "beam_topk_rows")
+
+
+def beam_advance(cand_score: torch.Tensor, cand_token: torch.Tensor, cand_logprob: torch.Tensor, n_examples: int, beams: int, step: int,
+                 eos: int, pad: int, length_penalty: float, early_stopping: bool, score: torch.Tensor, rank_of_slot: torch.Tensor,
+                 state: torch.Tensor, pos_rows: Optional[torch.Tensor], cur_len: torch.Tensor, next_ids: torch.Tensor, heap: torch.Tensor,
+                 heap_meta: torch.Tensor, done: torch.Tensor, trellis: torch.Tensor, pairs: torch.Tensor, pair_count: torch.Tensor) -> None:
+    """One beam-search step of every example from the sorted candidates of its ``beams`` slots (:func:`beam_topk_rows`, row = slot): the
+    next beams and their slots, the finished-hypothesis heap, the done flags, row ``step`` of the trellis and the K/V copy list, all on the
+    device.  Shapes and rules: include/llark_hip.h (llark_beam_advance)."""
+    i32, f32 = torch.int32, torch.float32
+    slots = n_examples * beams
+    assert all(t.numel() == slots * 2 * beams for t in (cand_score, cand_token, cand_logprob))
+    assert all(t.numel() == slots for t in (score, rank_of_slot, state, next_ids)) and (pos_rows is None or pos_rows.numel() == slots)
+    assert cur_len.numel() == n_examples and done.numel() == n_examples and pair_count.numel() == n_examples
+    assert heap.numel() == slots * BEAM_HEAP_STRIDE and heap_meta.numel() == n_examples * BEAM_META_STRIDE
+    assert trellis.dim() == 3 and trellis.shape[1:] == (slots, 3) and pairs.numel() == n_examples * max(beams - 1, 1) * 2
+    check(_lib.lib().llark_beam_advance(_dev(cand_score, "cand_score", f32), _dev(cand_token, "cand_token", i32),
+                                        _dev(cand_logprob, "cand_logprob", f32), int(n_examples), int(beams), int(step), trellis.shape[0],
+                                        int(eos), int(pad), float(length_penalty), int(bool(early_stopping)), _dev(score, "score", f32),
+                                        _dev(rank_of_slot, "rank_of_slot", i32), _dev(state, "state", i32), _opt(pos_rows, "pos_rows", i32),
+                                        _dev(cur_len, "cur_len", i32), _dev(next_ids, "next_ids", torch.int64), _dev(heap, "heap", i32),
+                                        _dev(heap_meta, "heap_meta", i32), _dev(done, "done", i32), _dev(trellis, "trellis", i32),
+                                        _dev(pairs, "pairs", i32), _dev(pair_count, "pair_count", i32), _stream()), "beam_advance")
+
+
+def kv_copy_slots(k_cache: torch.Tensor, vt_cache: torch.Tensor, pairs: torch.Tensor, count: torch.Tensor, p0: torch.Tensor,
+                  pos_rows: torch.Tensor, max_span: int, k_cache_lo=None, vt_cache_lo=None) -> None:
+    """For every (src, dst) of a copy table on the device -- ``pairs`` int32 [n_lists, stride, 2], entry i of list l taken while i <
+    ``count[l]`` (int32 [n_lists]) -- positions [p0[dst], pos_rows[src]) of cache slot src into slot dst, all layers and planes, one launch,
+    nothing read back.  ``max_span``: the caller's upper bound on a span (sizes the grid).  Whole caches as in :func:`kv_copy_prefix`."""
+    bf, i32 = torch.bfloat16, torch.int32
+    assert k_cache.dim() == 5 and vt_cache.dim() == 5
+    layers, slots, nh, smax, hd = k_cache.shape
+    assert vt_cache.shape == (layers, slots, nh, hd, smax)
+    for c, ref in ((k_cache_lo, k_cache), (vt_cache_lo, vt_cache)):
+        assert c is None or c.shape == ref.shape
+    assert pairs.dim() == 3 and pairs.shape[2] == 2 and count.numel() == pairs.shape[0] and p0.numel() == slots and pos_rows.numel() == slots
+    with _timed("kv_copy_slots", 0.0):
+        check(_lib.lib().llark_kv_copy_slots(_dev(k_cache, "k_cache", bf), _dev(vt_cache, "vt_cache", bf), _opt(k_cache_lo, "k_cache_lo", bf),
+                                             _opt(vt_cache_lo, "vt_cache_lo", bf), layers, slots, nh, hd, smax, _dev(pairs, "pairs", i32),
+                                             _dev(count, "count", i32), pairs.shape[0], pairs.shape[1], _dev(p0, "p0", i32),
+                                             _dev(pos_rows, "pos_rows", i32), int(max_span), _stream()), "kv_copy_slots")
+
+
 # ------------------------------------------------------------------------------------------------
 # MPT
 # ------------------------------------------------------------------------------------------------
