@@ -663,6 +663,48 @@ int llark_beam_advance(const float* cand_score, const int* cand_token, const flo
 int llark_kv_copy_slots(void* k_cache, void* vt_cache, void* k_cache_lo, void* vt_cache_lo, int layers, int slots, int nh, int hd, int smax,
                         const int* pairs, const int* count, int n_lists, int list_stride, const int* p0, const int* pos_rows, int max_span,
                         llark_stream_t stream);
+/* Constrained decoding on the device (csrc/constrain.hip): the tokens that HF 4.29.2's NoRepeatNGram, NoBadWords, MinLength and
+ * MinNewTokensLength processors ban for a row's next choice, from the row's token history, which lives in device memory.
+ *   llark_constrain_rows: one workgroup of 1024 threads per row r of logits fp32 [rows][ldl]; slot_of_row, state and the skip rules are
+ *     those of llark_token_logprob_rows (a skipped row: nothing read, nothing written, its history untouched).  Per-slot state: hist int32
+ *     [slots][ld_hist], hist_len int32 [slots], prompt_len int32 [slots] (nullable: 0).  hist == NULL (then hist_len, prompt_len, parent and
+ *     last_token are NULL too): every row has the empty history.  In order, with L = hist_len[slot] clamped to [0, ld_hist]:
+ *       1. fork: parent (nullable) is int32 with an element stride -- entry of a slot at parent[slot * parent_stride], so column 0 of a
+ *          trellis row of llark_beam_advance can be passed as it lies.  p = that entry; p outside [0, slots) counts as p = slot.  When p !=
+ *          slot, hist[p][0 .. L) is copied into hist[slot]: the slot's OWN length, since the beams of an example advance together and
+ *          hist_len[p] is being written by another workgroup.  Race-free in place by the slot rule of llark_beam_advance: a slot that is
+ *          read keeps its own beam this step, and the only write to its row is at position L.
+ *       2. append: last_token int64 [slots] (nullable: a prefill row, whose history is its prompt) holds the token this row's logits were
+ *          computed from: hist[slot][L] = it, hist_len[slot] = L + 1.  When L == ld_hist nothing is appended and bit 0 of *status
+ *          (nullable) is set; nothing is ever written outside the row.  An id outside int32 is stored as -1.
+ *       3. bans, over the history h[0 .. L') after the append:
+ *          no_repeat_ngram = n (0: off), when L' + 1 >= n: x is banned if some i in [0, L' - n] has h[i .. i+n-1) == h[L'-n+1 .. L') and
+ *            x == h[i+n-1]; n = 1 bans every token of the history;
+ *          bad words: a flat table bw_tokens int32 [bw_total] with bw_off int32 [n_words + 1] (word w = bw_tokens[bw_off[w] .. bw_off[w+1]),
+ *            k tokens), when k - 1 <= L': x = w[k-1] is banned if h[L'-k+1 .. L') == w[0 .. k-1) (4.29.2's _tokens_match); a word whose
+ *            offsets are not 0 <= bw_off[w] < bw_off[w+1] <= bw_total is ignored;
+ *          eos (>= 0) is banned while L' - prompt_len[slot] < min_new_tokens or L' < min_length.
+ *          A history or table token outside [0, vocab) takes part in comparisons and never bans anything.
+ *       4. outputs, each nullable but not all three: out fp32 [rows][ldo] = the row's raw bits, -inf at banned columns (columns >= vocab
+ *          are not written); ban uint32 [slots][ld_ban], row of the SLOT: bit (t & 31) of word t >> 5, words [0, ceil(vocab / 32));
+ *          n_banned int32 [rows].
+ *     Caps: vocab <= 65536 (LLARK_ERR_UNSUPPORTED above, as llark_sample_rows), no_repeat_ngram <= 64, n_words <= 4096, bw_total <= 2^20.
+ *     LLARK_ERR_INVALID before any launch: a null logits, all of out / ban / n_banned null, rows, slots or vocab <= 0, ldl < vocab, rows >
+ *     slots without slot_of_row, hist without hist_len or the reverse, ld_hist <= 0 with hist, parent / last_token / prompt_len without
+ *     hist, parent_stride < 1, no_repeat_ngram outside 0 .. 64 or > 0 without hist, a word table above the caps, with bw_total < n_words
+ *     or without its pointers, a negative min_new_tokens / min_length, ldo < vocab, ld_ban < ceil(vocab / 32).
+ *     No workgroup waits for another; no global atomics (the bitmap is built in LDS).
+ *   llark_beam_topk_rows_banned: llark_beam_topk_rows with ban uint32 [slots][ld_ban] as llark_constrain_rows writes it: a banned column
+ *     is left out of the selection only -- it still counts in M and S, so cand_logprob stays bit-equal to llark_token_logprob_rows.  A row
+ *     with fewer than 2B columns left fills the rest with (-inf, -1, -inf).  LLARK_ERR_INVALID additionally: a null ban, ld_ban too small. */
+int llark_constrain_rows(const float* logits, int ldl, int vocab, int rows, int slots, const int* state, const int* slot_of_row, int* hist,
+                         int ld_hist, int* hist_len, const int* prompt_len, const int* parent, int parent_stride, const int64_t* last_token,
+                         int no_repeat_ngram, const int* bw_tokens, const int* bw_off, int n_words, int bw_total, int64_t eos,
+                         int min_new_tokens, int min_length, float* out, int ldo, unsigned* ban, int ld_ban, int* n_banned, int* status,
+                         llark_stream_t stream);
+int llark_beam_topk_rows_banned(const float* logits, int ldl, int vocab, int rows, int slots, const int* state, const int* slot_of_row,
+                                const float* score, int beams, float* cand_score, int* cand_token, float* cand_logprob, int* fallbacks,
+                                const unsigned* ban, int ld_ban, llark_stream_t stream);
 /* MPT ragged decode step, the whole attention front in one launch (m2t/llava/model/mpt/attention.py: qkv.clamp_ -> q_ln / k_ln ->
  * head split -> attention with the ALiBi bias; replaces llark_clamp_f32 + 2 x llark_layernorm_f32 + llark_attn_decode_rope_bf16_rows
  * with identity tables).  qkv fp32 [batch][ldq], laid out q | k | v with nh*128 columns each, is READ ONLY.  Workgroup (h, b) reads

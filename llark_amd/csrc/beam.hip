@@ -35,6 +35,8 @@ struct BeamTopkArgs {
     int* cand_token;
     float* cand_logprob;
     int* fallbacks;
+    const unsigned* ban;                                          // BAN instantiation only: uint32 [slots][ld_ban]
+    int ld_ban;
 };
 
 // order-preserving image of a non-NaN float: a < b  <=>  key(a) < key(b); -inf -> 0x007fffff, so 0 lies below every float
@@ -47,7 +49,8 @@ __device__ __forceinline__ unsigned long long beam_comp(float cand, int token) {
 }
 __device__ __forceinline__ unsigned long long beam_max_u64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
 
-template <int NPT>
+// BAN: a column whose bit of ban[slot] is set gets key 0 -- it is left out of the selection and still counts in M and S
+template <int NPT, bool BAN = false>
 __global__ __launch_bounds__(BEAM_THREADS) void beam_topk_rows_kernel(const BeamTopkArgs a) {
     __shared__ float smax[BEAM_WAVES];
     __shared__ int sbad[BEAM_WAVES];
@@ -118,14 +121,17 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_topk_rows_kernel(const Beam
     // ---- selection: K rounds of a block maximum over the keys below the last winner ---------------------------------------------------
     // + 0: -0 becomes +0, so the key order is the float order
 #define BEAM_CAND(x) ((score + (((x) - M) - logS)) + 0.0f)
+    const unsigned* banw = nullptr;
+    if constexpr (BAN) banw = a.ban + (size_t)slot * a.ld_ban;
+#define BEAM_KEY(x, j) (BAN && ((banw[(j) >> 5] >> ((j) & 31)) & 1u) ? 0ull : beam_comp(BEAM_CAND(x), (int)(j)))
     unsigned long long mine = 0ull;
 #pragma unroll
     for (int i = 0; i < NPT; ++i) {
         const int j = tid + BEAM_THREADS * i;
-        if (j < vocab) mine = beam_max_u64(mine, beam_comp(BEAM_CAND(v[i]), j));
+        if (j < vocab) mine = beam_max_u64(mine, BEAM_KEY(v[i], j));
     }
     for (long long j = (long long)NPT * BEAM_THREADS + tid; j < vocab; j += BEAM_THREADS)
-        mine = beam_max_u64(mine, beam_comp(BEAM_CAND(row[j]), (int)j));
+        mine = beam_max_u64(mine, BEAM_KEY(row[j], j));
     int parity = 0;
 #pragma unroll 1
     for (int k = 0; k < K; ++k) {
@@ -144,11 +150,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_topk_rows_kernel(const Beam
 #pragma unroll
             for (int i = 0; i < NPT; ++i) {
                 const int j = tid + BEAM_THREADS * i;
-                const unsigned long long c = j < vocab ? beam_comp(BEAM_CAND(v[i]), j) : 0ull;
+                const unsigned long long c = j < vocab ? BEAM_KEY(v[i], j) : 0ull;
                 if (c < w) nxt = beam_max_u64(nxt, c);
             }
             for (long long j = (long long)NPT * BEAM_THREADS + tid; j < vocab; j += BEAM_THREADS) {
-                const unsigned long long c = beam_comp(BEAM_CAND(row[j]), (int)j);
+                const unsigned long long c = BEAM_KEY(row[j], j);
                 if (c < w) nxt = beam_max_u64(nxt, c);
             }
             mine = nxt;
@@ -157,7 +163,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_topk_rows_kernel(const Beam
     __syncthreads();
     if (tid < K) {
         const unsigned long long w = swin[tid];
-        if (w == 0ull) {                                          // vocab >= K: cannot happen; never an index out of the row
+        if (w == 0ull) {                                          // fewer than K columns left (only under bans): never an index out of the row
             out_s[tid] = -INFINITY, out_t[tid] = -1, out_l[tid] = -INFINITY;
         } else {
             const int t = (int)(0xffffffffu - (unsigned)(w & 0xffffffffull));
@@ -167,6 +173,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_topk_rows_kernel(const Beam
             out_l[tid] = lp;
         }
     }
+#undef BEAM_KEY
 #undef BEAM_CAND
 }
 
@@ -357,11 +364,32 @@ extern "C" int llark_beam_topk_rows(const float* logits, int ldl, int vocab, int
     BeamTopkArgs a;
     a.logits = logits, a.ldl = ldl, a.vocab = vocab, a.slots = slots, a.k = 2 * beams, a.state = state, a.slot_of_row = slot_of_row;
     a.score = score, a.cand_score = cand_score, a.cand_token = cand_token, a.cand_logprob = cand_logprob, a.fallbacks = fallbacks;
+    a.ban = nullptr, a.ld_ban = 0;
     hipStream_t st = (hipStream_t)stream;
     if (vocab <= 4 * BEAM_THREADS) beam_topk_rows_kernel<4><<<rows, BEAM_THREADS, 0, st>>>(a);
     else if (vocab <= 32 * BEAM_THREADS) beam_topk_rows_kernel<32><<<rows, BEAM_THREADS, 0, st>>>(a);
     else beam_topk_rows_kernel<50><<<rows, BEAM_THREADS, 0, st>>>(a);
     return check_launch("beam_topk_rows");
+}
+
+extern "C" int llark_beam_topk_rows_banned(const float* logits, int ldl, int vocab, int rows, int slots, const int* state,
+                                           const int* slot_of_row, const float* score, int beams, float* cand_score, int* cand_token,
+                                           float* cand_logprob, int* fallbacks, const unsigned* ban, int ld_ban, llark_stream_t stream) {
+    LLARK_REQUIRE(logits && score && cand_score && cand_token && cand_logprob && ban,
+                  "beam_topk_rows_banned: null pointer (logits, score, cand_score, cand_token, cand_logprob, ban)");
+    LLARK_REQUIRE(beams >= 1 && beams <= BEAM_MAX, "beam_topk_rows_banned: beams=%d outside 1 .. %d", beams, BEAM_MAX);
+    LLARK_REQUIRE(rows > 0 && slots > 0 && vocab >= 2 * beams && ldl >= vocab && (slot_of_row || rows <= slots),
+                  "beam_topk_rows_banned: bad shape rows=%d slots=%d vocab=%d (>= 2 beams = %d) ldl=%d", rows, slots, vocab, 2 * beams, ldl);
+    LLARK_REQUIRE(ld_ban >= (vocab + 31) / 32, "beam_topk_rows_banned: ld_ban=%d below ceil(vocab / 32)=%d", ld_ban, (vocab + 31) / 32);
+    BeamTopkArgs a;
+    a.logits = logits, a.ldl = ldl, a.vocab = vocab, a.slots = slots, a.k = 2 * beams, a.state = state, a.slot_of_row = slot_of_row;
+    a.score = score, a.cand_score = cand_score, a.cand_token = cand_token, a.cand_logprob = cand_logprob, a.fallbacks = fallbacks;
+    a.ban = ban, a.ld_ban = ld_ban;
+    hipStream_t st = (hipStream_t)stream;
+    if (vocab <= 4 * BEAM_THREADS) beam_topk_rows_kernel<4, true><<<rows, BEAM_THREADS, 0, st>>>(a);
+    else if (vocab <= 32 * BEAM_THREADS) beam_topk_rows_kernel<32, true><<<rows, BEAM_THREADS, 0, st>>>(a);
+    else beam_topk_rows_kernel<50, true><<<rows, BEAM_THREADS, 0, st>>>(a);
+    return check_launch("beam_topk_rows_banned");
 }
 
 extern "C" int llark_beam_advance(const float* cand_score, const int* cand_token, const float* cand_logprob, int n_examples, int beams,

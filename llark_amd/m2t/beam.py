@@ -72,6 +72,9 @@ class BeamSearch:
         self.p0_host: List[int] = [0] * N
         # test hooks: observe_logits(step, logits) before the step's launches, observe_move(step, "before" / "after") around the K/V move
         self.observe_logits = self.observe_move = None
+        # a llark_amd.m2t.constraints.DeviceConstraints over the same slots (admitted by the caller): banned tokens are left out of the
+        # candidates; None: the unconstrained launch
+        self.constraints = None
 
     def admit(self, prompt_lens: Sequence[int]) -> None:
         """The examples' prompt lengths: cur_len, and the first position a K/V move has to copy (the slots of an example are clones of
@@ -83,19 +86,28 @@ class BeamSearch:
         self.cur_len.copy_(torch.tensor(lens, dtype=torch.int32))
         self.p0.copy_(torch.tensor(self.p0_host, dtype=torch.int32).repeat_interleave(self.beams))
 
-    def step(self, logits: torch.Tensor, state: torch.Tensor, pos_rows: Optional[torch.Tensor] = None, kv=None) -> Tuple[torch.Tensor, List[bool]]:
+    def step(self, logits: torch.Tensor, state: torch.Tensor, pos_rows: Optional[torch.Tensor] = None, kv=None,
+             last: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, List[bool]]:
         """One step from fp32 ``logits`` [slots, >= vocab] (row = slot).  ``state``: the slots' ROW_* states; ``pos_rows``: their cache
         lengths, advanced by one for the rows of examples that are not done (None: nothing advances); ``kv`` = (k_cache, vt_cache,
-        k_cache_lo, vt_cache_lo): the caches in which forked beams receive their parent's positions (None: no move).  Returns (next ids
-        [slots] on the device, the examples' done flags on the host)."""
+        k_cache_lo, vt_cache_lo): the caches in which forked beams receive their parent's positions (None: no move).  ``last`` (with
+        ``constraints``): the ids the logits were computed from, None on the prompts' logits; a slot's history then follows its beam --
+        the parent column of the previous trellis row says whose history it continues.  Returns (next ids [slots] on the device, the
+        examples' done flags on the host)."""
         if self.steps >= self.max_steps:
             raise RuntimeError(f"BeamSearch.step: all {self.max_steps} steps are used")
         assert logits.shape[0] == self.slots and logits.shape[1] >= self.vocab
         N, B = self.n, self.beams
         if self.observe_logits is not None:
             self.observe_logits(self.steps, logits)
+        ban = None
+        if self.constraints is not None:
+            if (last is None) != (self.steps == 0):
+                raise ValueError("BeamSearch.step: constraints need `last` on every step but the first")
+            ban = self.constraints.process(logits, state=state, last=last, parent=None if last is None else self.trellis[self.steps - 1, :, 0],
+                                           bitmap=True)
         ops.beam_topk_rows(logits, self.score, B, self.cand_score, self.cand_token, self.cand_logprob, vocab=self.vocab, state=state,
-                           fallbacks=self.fallbacks)
+                           fallbacks=self.fallbacks, **({} if ban is None else dict(ban=ban)))
         ops.beam_advance(self.cand_score, self.cand_token, self.cand_logprob, N, B, self.steps, self.eos, self.pad, self.length_penalty,
                          self.early_stopping, self.score, self.rank_of_slot, state, pos_rows, self.cur_len, self.next_ids, self.heap,
                          self.heap_meta, self.done, self.trellis, self.pairs, self.pair_count)

@@ -1032,7 +1032,10 @@ class HipLlamaEngine:
         B = beam.beams
         was_done = list(beam.done_host)
         kv = None if first else (self.k_cache, self.vt_cache, self.k_cache_lo, self.vt_cache_lo)
-        nxt, done = beam.step(logits, self.slot_state, None if first else self.slot_len, kv)
+        if getattr(beam, "constraints", None) is not None:
+            nxt, done = beam.step(logits, self.slot_state, None if first else self.slot_len, kv, last=ids)
+        else:
+            nxt, done = beam.step(logits, self.slot_state, None if first else self.slot_len, kv)
         for e, (w, dn) in enumerate(zip(was_done, done)):
             for b in range(e * B, e * B + B):
                 if not w and not first:

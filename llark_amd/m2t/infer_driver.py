@@ -59,15 +59,19 @@ def build_prompt_ids(prompt: str, frames: int, tokenizer, multimodal_cfg: Dict[s
 
 @torch.no_grad()
 def generate_batch(model, input_ids: torch.Tensor, encodings: torch.Tensor, tokenizer, max_new_tokens: int = 512,
-                   keywords: Sequence[str] = ("###",)) -> List[torch.Tensor]:
+                   keywords: Sequence[str] = ("###",), **generate_kwargs) -> List[torch.Tensor]:
     """Greedy generation for B examples sharing one prompt length.  Returns, per example, prompt + continuation ids cut
-    where the reference's loop would have stopped for that example (keyword hit, EOS, or ``max_new_tokens``)."""
+    where the reference's loop would have stopped for that example (keyword hit, EOS, or ``max_new_tokens``).  ``generate_kwargs``
+    (``no_repeat_ngram_size``, ``min_new_tokens``, ...) go to ``model.generate``.  EOS is handled per row here and ``generate`` runs
+    without one -- except under ``min_new_tokens`` / ``min_length``, which ban the EOS and so need ``generate`` to know it: a row that
+    ended then emits padding behind its cut, nothing else changes."""
     B = input_ids.shape[0]
     dev = model.engine.device if getattr(model, "_engine", None) is not None else torch.device("cuda")
     ids = input_ids.to(dev)
     stops = [KeywordsStoppingCriteria(keywords=list(keywords), tokenizer=tokenizer, input_ids=input_ids[b: b + 1]) for b in range(B)]
     eos = getattr(getattr(model, "generation_config", None), "eos_token_id", None)
     done_at: List[Optional[int]] = [None] * B
+    needs_eos = eos is not None and bool(generate_kwargs.get("min_new_tokens") or generate_kwargs.get("min_length"))
 
     class _AllDone:                                        # plugs the per-row bookkeeping into model.generate's loop
         def __call__(self, out_ids, scores=None, **kw):
@@ -79,23 +83,24 @@ def generate_batch(model, input_ids: torch.Tensor, encodings: torch.Tensor, toke
             return all(d is not None for d in done_at)
 
     out = model.generate(input_ids=ids, audio_encodings=encodings, max_new_tokens=max_new_tokens, stopping_criteria=[_AllDone()],
-                         eos_token_id=-1)                  # EOS is handled per row above
+                         eos_token_id=eos if needs_eos else -1, **generate_kwargs)     # EOS is handled per row above
     out = out.cpu()
     return [out[b, : (done_at[b] if done_at[b] is not None else out.shape[1])] for b in range(B)]
 
 
 @torch.no_grad()
 def generate_beam(model, input_ids: torch.Tensor, encodings: torch.Tensor, tokenizer, max_new_tokens: int = 512, num_beams: int = 4,
-                  length_penalty: float = 1.0, keywords: Sequence[str] = ("###",)) -> List[torch.Tensor]:
+                  length_penalty: float = 1.0, keywords: Sequence[str] = ("###",), **generate_kwargs) -> List[torch.Tensor]:
     """Beam search, one example per ``model.generate(num_beams=...)`` call under the keyword stopping criterion (HF's criterion sees
     the best live beam first, as the reference's loop would).  Returns, per example, prompt + the best hypothesis' ids: the eos that
-    generate puts behind a short row, and the padding, are cut."""
+    generate puts behind a short row, and the padding, are cut.  ``generate_kwargs`` (``no_repeat_ngram_size``, ``min_new_tokens``, ...) go to
+    ``model.generate``."""
     eos = getattr(getattr(model, "generation_config", None), "eos_token_id", None)
     S, outs = input_ids.shape[1], []
     for b in range(input_ids.shape[0]):
         stop = KeywordsStoppingCriteria(keywords=list(keywords), tokenizer=tokenizer, input_ids=input_ids[b: b + 1])
         row = model.generate(input_ids=input_ids[b: b + 1], audio_encodings=encodings[b: b + 1], max_new_tokens=max_new_tokens,
-                             stopping_criteria=[stop], num_beams=num_beams, length_penalty=length_penalty)[0].cpu()
+                             stopping_criteria=[stop], num_beams=num_beams, length_penalty=length_penalty, **generate_kwargs)[0].cpu()
         hit = (row[S:] == eos).nonzero() if eos is not None and eos >= 0 else torch.empty((0, 1))
         outs.append(row[: S + int(hit[0])] if hit.numel() else row)
     return outs
@@ -275,9 +280,12 @@ class EngineSlots:
     sampler, whose stream id is the example's input index.  ``logprobs``: every token handed out -- the first one from the refill's
     prefill logits, the others from the decode step's -- gets its log-probability under the model's raw logits (log-softmax; no
     repetition penalty, temperature, top-k or top-p, for sampled tokens too) appended to its slot's history on the device
-    (:class:`llark_amd.m2t.logprob.LogprobTracker`, one launch per step); ``take_logprobs(slots)`` reads finished slots' histories."""
+    (:class:`llark_amd.m2t.logprob.LogprobTracker`, one launch per step); ``take_logprobs(slots)`` reads finished slots' histories.
+    ``constraints`` (a :class:`llark_amd.m2t.constraints.TokenConstraints`): every choice, greedy or sampled, is made on the logits with
+    -inf at the tokens its example's history bans (one more launch per step, no transfer); the EOS of ``min_new_tokens`` /
+    ``min_length`` is the model's ``generation_config.eos_token_id``."""
 
-    def __init__(self, model, n_slots: int, share_prefix: bool = False, sampling=None, logprobs: bool = False):
+    def __init__(self, model, n_slots: int, share_prefix: bool = False, sampling=None, logprobs: bool = False, constraints=None):
         from .llamav2 import plan_audio_splice
 
         self._plan = plan_audio_splice
@@ -293,6 +301,8 @@ class EngineSlots:
         self.sampler = None                                       # built at the first prefill, which tells the logits' width
         self.logprobs = bool(logprobs)
         self.tracker = None                                       # likewise
+        self.constraints = constraints if constraints is not None and constraints.active else None
+        self.cons = None                                          # likewise
         cfg = model.get_model().audio_encoder_config
         self.audio_token_ids = tuple(int(t) for t in (getattr(cfg, name, None) for name in ("audio_start_token", "audio_end_token", "audio_patch_token"))
                                      if t is not None)
@@ -312,6 +322,16 @@ class EngineSlots:
             logits = eng.prefill_slots([p.to(eng.device) for p in prompts], segs, slots)
         else:
             logits = eng.prefill_slots([p.to(eng.device) for p in prompts], segs, slots, past=past)
+        raw = logits
+        if self.constraints is not None:
+            if self.cons is None:
+                from .constraints import DeviceConstraints
+
+                eos = getattr(getattr(self.model, "generation_config", None), "eos_token_id", None)
+                # a history is at most the cache's smax positions plus the token just chosen: the engine refuses a slot beyond smax first
+                self.cons = DeviceConstraints(self.constraints, eng.n_slots, logits.shape[-1], eng.smax + 1, eng.device, eos)
+            self.cons.admit(slots, prompts if whole is None else whole)
+            logits = self.cons.process(raw, state=eng.slot_state, slot_of_row=list(slots))
         if self.sampling is not None:
             if self.sampler is None:
                 from .sampling import DeviceSampler
@@ -321,6 +341,7 @@ class EngineSlots:
             first = self.sampler(logits, state=eng.slot_state, slot_of_row=list(slots))
         else:
             first = logits.argmax(-1)                              # what generate() picks after the prompt
+        logits = raw                                               # log-probabilities: the model's own distribution
         if self.logprobs:
             if self.tracker is None:
                 from .logprob import LogprobTracker
@@ -332,19 +353,20 @@ class EngineSlots:
         return first.cpu().tolist()
 
     def decode(self):
-        if self.sampler is not None or self.tracker is not None:
+        if self.sampler is not None or self.tracker is not None or self.cons is not None:
             self.ids, host, _ = self.eng.decode_slots(self.ids, sample=self._sample)
         else:
             self.ids, host, _ = self.eng.decode_slots(self.ids)
         return host.tolist()
 
     def _sample(self, logits):
+        rows = logits if self.cons is None else self.cons.process(logits, state=self.eng.slot_state, last=self.ids)
         if self.sampler is not None:
-            tokens = self.sampler(logits, state=self.eng.slot_state)
+            tokens = self.sampler(rows, state=self.eng.slot_state)
         else:                                                      # the advance kernel's own rule: the first maximal index
             from .. import ops
 
-            tokens = ops.sample_rows(logits, torch.zeros((logits.shape[0],), dtype=torch.int64, device=logits.device),
+            tokens = ops.sample_rows(rows, torch.zeros((rows.shape[0],), dtype=torch.int64, device=rows.device),
                                      state=self.eng.slot_state, do_sample=False, repetition_penalty=1.0)
         if self.tracker is not None:
             self.tracker(logits, tokens, state=self.eng.slot_state)
@@ -359,13 +381,15 @@ class EngineSlots:
         self.eng.release_slots(slots)
         if self.sampler is not None:
             self.sampler.release(slots)
+        if self.cons is not None:
+            self.cons.release(slots)
 
 
 @torch.no_grad()
 def generate_inflight(model, examples: Iterable[Sequence[Any]], slots: int = 8, max_new_tokens: int = 512,
                       keywords: Sequence[str] = ("###",), tokenizer=None, trace: Optional[list] = None,
                       share_prefix: bool = False, sampling=None, return_logprobs: bool = False,
-                      num_beams: Optional[int] = None) -> Iterator[Tuple[int, torch.Tensor]]:
+                      num_beams: Optional[int] = None, constraints=None) -> Iterator[Tuple[int, torch.Tensor]]:
     """Generation (greedy unless ``sampling``) with in-flight slot refill.  ``examples`` yields ``(prompt_ids, encoding[, max_new_tokens[, prefix_key]])`` with prompts
     of any length; up to ``slots`` of them decode together, each at its own KV-cache length, and a finished row's slot is refilled
     from the iterable (contiguous free slots prefilled as one batch) while the others keep decoding.  Stops per row as in
@@ -380,7 +404,11 @@ def generate_inflight(model, examples: Iterable[Sequence[Any]], slots: int = 8, 
     ``logprobs`` (1-D fp32, CPU) has one entry per generated token, ``ids.numel() - prompt.numel()`` of them, the EOS or keyword token
     included.  They are log-probabilities of the MODEL's distribution: log-softmax of the raw logits, computed on the device in the
     step's own launch sequence (``llark_token_logprob_rows``); repetition penalty, temperature, top-k and top-p are not applied, for
-    sampled tokens too.  Refused with a model's own ``slot_backend`` as sampling is."""
+    sampled tokens too.  Refused with a model's own ``slot_backend`` as sampling is.  ``constraints``: a
+    :class:`llark_amd.m2t.constraints.TokenConstraints` (``no_repeat_ngram_size``, ``bad_words_ids``, ``suppress_tokens``,
+    ``min_new_tokens``, ``min_length``), applied on the device to every choice from the example's own history -- its whole prompt under
+    ``share_prefix`` too -- so a completion does not depend on ``slots``; an example's own ``max_new_tokens`` below ``min_new_tokens``
+    wins: the row stops at its budget.  Refused with a model's own ``slot_backend`` as sampling is."""
     refuse_beams("generate_inflight", num_beams)
     if keywords and tokenizer is None:
         raise ValueError("generate_inflight: keyword stopping needs the tokenizer")
@@ -390,12 +418,16 @@ def generate_inflight(model, examples: Iterable[Sequence[Any]], slots: int = 8, 
         raise ValueError("generate_inflight: sampling needs the engine's own slot backend; this model provides slot_backend()")
     if return_logprobs and make is not None:
         raise ValueError("generate_inflight: return_logprobs needs the engine's own slot backend; this model provides slot_backend()")
+    constraints = constraints if constraints is not None and constraints.active else None
+    if constraints is not None and make is not None:
+        raise ValueError("generate_inflight: constraints need the engine's own slot backend; this model provides slot_backend()")
+    more = {} if constraints is None else dict(constraints=constraints)
     if make is not None:
         backend = make(slots)
     elif return_logprobs:
-        backend = EngineSlots(model, slots, share_prefix, sampling, logprobs=True)
+        backend = EngineSlots(model, slots, share_prefix, sampling, logprobs=True, **more)
     else:
-        backend = EngineSlots(model, slots, share_prefix, sampling)
+        backend = EngineSlots(model, slots, share_prefix, sampling, **more)
     eos = getattr(getattr(model, "generation_config", None), "eos_token_id", None)
     stop_fn = None
     if keywords:
@@ -403,7 +435,8 @@ def generate_inflight(model, examples: Iterable[Sequence[Any]], slots: int = 8, 
             if row["stop"] is None:
                 row["stop"] = KeywordsStoppingCriteria(keywords=list(keywords), tokenizer=tokenizer, input_ids=row["prompt"][None])
             return bool(row["stop"](torch.cat((row["prompt"], gen))[None], None))
-    sched = InflightScheduler(backend, slots, max_new_tokens, eos, stop_fn, share_prefix=share_prefix, sampling=sampling is not None,
+    sched = InflightScheduler(backend, slots, max_new_tokens, eos, stop_fn, share_prefix=share_prefix,
+                              sampling=sampling is not None or constraints is not None,
                               **(dict(logprobs=True) if return_logprobs else {}))
     if trace is not None:
         sched.trace = trace
@@ -493,10 +526,16 @@ def _write_csv(records: List[Dict[str, str]], outfile: Optional[str]) -> None:
 def infer_from_encodings(model, tokenizer, audio_encodings_dir: str, prompt: str, multimodal_cfg: Dict[str, Any],
                          end_seq: Sequence[int], outfile: Optional[str] = None, batch_size: int = 8,
                          max_samples: Optional[int] = None, max_new_tokens: int = 512, audio_first: bool = True,
-                         embed_dim: Optional[int] = None, num_beams: int = 1, length_penalty: float = 1.0) -> List[Dict[str, str]]:
+                         embed_dim: Optional[int] = None, num_beams: int = 1, length_penalty: float = 1.0,
+                         no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None) -> List[Dict[str, str]]:
     """Directory of ``*.npy`` -> CSV, like ``scripts/inference/infer_from_encodings.py:main`` (same record fields; files
     in sorted order; ``example_id`` = path without ``.npy``).  Examples are grouped by frame count so that every batch
-    shares one prompt length.  ``num_beams`` > 1: beam search with ``length_penalty``, one example per call (:func:`generate_beam`)."""
+    shares one prompt length.  ``num_beams`` > 1: beam search with ``length_penalty``, one example per call (:func:`generate_beam`).
+    ``no_repeat_ngram_size`` / ``min_new_tokens`` go to ``model.generate`` on both paths (:mod:`llark_amd.m2t.constraints`)."""
+    from .constraints import constraints_from_generate
+
+    constraints_from_generate(no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens)      # bad values raise here, by name
+    more = {k: v for k, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_new_tokens", min_new_tokens)) if v}
     if embed_dim is None:                                  # 4800 for Jukebox, 512 for CLAP (ModelArguments.mm_hidden_size)
         embed_dim = int(getattr(getattr(model, "config", None), "mm_hidden_size", EMBED_DIM))
     paths = sorted(glob.glob(os.path.join(audio_encodings_dir, "*.npy")))
@@ -514,9 +553,9 @@ def infer_from_encodings(model, tokenizer, audio_encodings_dir: str, prompt: str
             enc = torch.from_numpy(np.stack([a for _, a in chunk])).cuda()
             ids = prompt_ids.unsqueeze(0).repeat(len(chunk), 1)
             if num_beams is not None and num_beams != 1:
-                outs = generate_beam(model, ids, enc, tokenizer, max_new_tokens, num_beams, length_penalty)
+                outs = generate_beam(model, ids, enc, tokenizer, max_new_tokens, num_beams, length_penalty, **more)
             else:
-                outs = generate_batch(model, ids, enc, tokenizer, max_new_tokens)
+                outs = generate_batch(model, ids, enc, tokenizer, max_new_tokens, **more)
             for rec in _rows_to_records([p[: -len(".npy")] for p, _ in chunk], prompt, outs, end_seq, tokenizer):
                 records[rec["example_id"]] = rec
     ordered = [records[p[: -len(".npy")]] for p in paths]
@@ -584,7 +623,7 @@ def infer_from_shards(model, tokenizer, shards: str, multimodal_cfg: Dict[str, A
                       slots: int = 8, max_samples: Optional[int] = None, max_new_tokens: int = 512, prompt: Optional[str] = None,
                       seed: int = 0, allow_pickle: bool = False, header: str = DEFAULT_CONVERSATION_HEADER,
                       share_prefix: bool = False, sampling=None, logprobs: bool = False,
-                      num_beams: Optional[int] = None) -> List[Dict[str, str]]:
+                      num_beams: Optional[int] = None, constraints=None) -> List[Dict[str, str]]:
     """Local tar shards -> CSV under the contract of ``scripts/inference/infer_from_webdataset.py:51-151``: every (question,
     answer) pair of a sample is one example whose prompt is its own human turn up to "### Assistant:" (audio placeholder first
     or last by a draw seeded with ``seed``); ``prompt`` overrides every question (the reference's ``--prompt``: audio first).
@@ -595,7 +634,8 @@ def infer_from_shards(model, tokenizer, shards: str, multimodal_cfg: Dict[str, A
     ``sampling``: a :class:`llark_amd.m2t.sampling.SamplingParams` (its ``seed`` is the draws'; ``seed`` here shuffles the questions).
     ``logprobs``: every record also gets ``sum_logprob``, ``mean_logprob`` and ``n_tokens`` over ALL generated tokens (the stop keyword or
     EOS included, although the completion text drops it): log-probabilities of the model's distribution -- log-softmax of the raw
-    logits; repetition penalty, temperature, top-k and top-p are not applied, for sampled tokens too."""
+    logits; repetition penalty, temperature, top-k and top-p are not applied, for sampled tokens too.  ``constraints``: a
+    :class:`llark_amd.m2t.constraints.TokenConstraints`, as in :func:`generate_inflight`."""
     from .data import element_to_conversations, expand_urls, iter_tar_samples
 
     refuse_beams("infer_from_shards", num_beams)
@@ -622,7 +662,8 @@ def infer_from_shards(model, tokenizer, shards: str, multimodal_cfg: Dict[str, A
     outs: Dict[int, torch.Tensor] = {}
     lps: Dict[int, torch.Tensor] = {}
     for item in generate_inflight(model, examples(), slots=slots, max_new_tokens=max_new_tokens, tokenizer=tokenizer,
-                                  share_prefix=share_prefix, sampling=sampling, **(dict(return_logprobs=True) if logprobs else {})):
+                                  share_prefix=share_prefix, sampling=sampling, **(dict(return_logprobs=True) if logprobs else {}),
+                                  **({} if constraints is None else dict(constraints=constraints))):
         outs[item[0]] = item[1]
         if logprobs:
             lps[item[0]] = item[2]
@@ -671,13 +712,22 @@ def main(argv=None):
     ap.add_argument("--llm-precision", default="split", choices=["split", "bf16"])
     ap.add_argument("--num_beams", type=int, default=1, help="beam search with this many beams (1 .. 16), one example per call; 1: greedy")
     ap.add_argument("--length_penalty", type=float, default=1.0, help="hypothesis score = sum of log-probabilities / length ** this")
+    ap.add_argument("--no_repeat_ngram_size", type=int, default=0, help="no n-gram of this size occurs twice in prompt + completion; 0: off")
+    ap.add_argument("--min_new_tokens", type=int, default=0, help="the EOS token is banned for this many new tokens; 0: off")
     for ignored in ("--ckpt-num", "--report_to", "--bf16", "--tf32", "--output_dir"):
         ap.add_argument(ignored, default=None, help="accepted for script compatibility")
     args = ap.parse_args(argv)
+    from .constraints import constraints_from_generate
+
+    try:                                                   # before the model is loaded
+        constraints_from_generate(no_repeat_ngram_size=args.no_repeat_ngram_size, min_new_tokens=args.min_new_tokens)
+    except ValueError as e:
+        ap.error(str(e))
     model, tok, end_seq, mm_cfg = _load_for_inference(args, max(args.batch_size, args.num_beams))
     recs = infer_from_encodings(model, tok, args.audio_encodings_dir, args.prompt, mm_cfg, end_seq, outfile=args.outfile,
                                 batch_size=args.batch_size, max_samples=args.max_samples, max_new_tokens=args.max_new_tokens,
-                                num_beams=args.num_beams, length_penalty=args.length_penalty)
+                                num_beams=args.num_beams, length_penalty=args.length_penalty,
+                                **{k: v for k, v in (("no_repeat_ngram_size", args.no_repeat_ngram_size), ("min_new_tokens", args.min_new_tokens)) if v})
     print(f"writing {len(recs)} results to {args.outfile}")
     return recs
 
@@ -731,6 +781,7 @@ def main_shards(argv=None):
     python -m llark_amd.m2t.infer_driver shards --model_name_or_path <dir> --eval_data_path "shards-{000000..000021}.tar" \
         --outfile results/infer.csv [--prompt "Describe ..."] [--max-samples N] [--max_new_tokens 2048] [--slots 8] [--allow-pickle]
         [--share-prefix] [--do-sample --temperature 0.8 --top-k 50 --top-p 0.9 --sample-seed 0] [--repetition-penalty 1.3] [--logprobs]
+        [--no-repeat-ngram-size 3] [--min-new-tokens 8]
     ``--allow-pickle``: read ``.pyd`` (pickled) encodings -- unpickling runs code, pass it only for shards you trust."""
     import argparse
 
@@ -758,17 +809,23 @@ def main_shards(argv=None):
     ap.add_argument("--num_beams", type=int, default=1, help="refused above 1: beam search is not scheduled in flight")
     ap.add_argument("--logprobs", action="store_true", help="add the columns sum_logprob, mean_logprob and n_tokens: log-probabilities of the "
                     "generated tokens under the model's raw logits (no penalty, temperature, top-k or top-p applied), computed on the device")
+    ap.add_argument("--no-repeat-ngram-size", type=int, default=0, help="no n-gram of this size occurs twice in prompt + completion "
+                    "(1 .. 64; 0: off); the bans are computed on the device from the example's own history")
+    ap.add_argument("--min-new-tokens", type=int, default=0, help="the EOS token is banned for this many new tokens (0: off); an example's "
+                    "own budget below it wins")
     ap.add_argument("--mm_hidden_size", type=int, default=None)
     ap.add_argument("--model_max_length", type=int, default=2048)
     ap.add_argument("--llm-precision", default="split", choices=["split", "bf16"])
     for ignored in ("--ckpt-num", "--report_to", "--bf16", "--tf32", "--output_dir"):
         ap.add_argument(ignored, default=None, help="accepted for script compatibility")
     args = ap.parse_args(argv)
+    from .constraints import constraints_from_generate
     from .sampling import SamplingParams
 
     try:
         sampling = SamplingParams(do_sample=args.do_sample, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
                                   repetition_penalty=args.repetition_penalty, seed=args.sample_seed)
+        constraints = constraints_from_generate(no_repeat_ngram_size=args.no_repeat_ngram_size, min_new_tokens=args.min_new_tokens)
     except ValueError as e:
         ap.error(str(e))
     if not 1 <= args.slots <= 64:
@@ -782,7 +839,8 @@ def main_shards(argv=None):
     recs = infer_from_shards(model, tok, args.eval_data_path, mm_cfg, end_seq, outfile=args.outfile, slots=args.slots,
                              max_samples=args.max_samples, max_new_tokens=args.max_new_tokens, prompt=args.prompt, seed=args.seed,
                              allow_pickle=args.allow_pickle, share_prefix=args.share_prefix, sampling=sampling if sampling.active else None,
-                             **(dict(logprobs=True) if args.logprobs else {}))
+                             **(dict(logprobs=True) if args.logprobs else {}),
+                             **({} if constraints is None else dict(constraints=constraints)))
     print(f"writing {len(recs)} results to {args.outfile}")
     return recs
 

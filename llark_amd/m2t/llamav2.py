@@ -26,6 +26,7 @@ from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutpu
 from .. import ops
 from . import AudioEncoderConfig
 from .beam import BeamSearch, check_beam_args
+from .constraints import DeviceConstraints, constraints_from_generate
 from .engine import HipLlamaEngine, LlamaDims
 from .logprob import ragged_logprob_hook, ragged_logprob_matrix
 from .sampling import DeviceSampler, params_from_generate
@@ -379,7 +380,8 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
                  top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, seed: Optional[int] = None,
                  return_logprobs: bool = False, num_beams: Optional[int] = None, length_penalty: float = 1.0,
                  early_stopping: bool = False, num_return_sequences: Optional[int] = None, num_beam_groups: Optional[int] = None,
-                 share_prefix: bool = False, **kwargs):
+                 share_prefix: bool = False, no_repeat_ngram_size: Optional[int] = None, bad_words_ids=None, suppress_tokens=None,
+                 min_new_tokens: Optional[int] = None, min_length: Optional[int] = None, **kwargs):
         """Greedy / temperature sampling loop with the semantics of HF 4.29.2 ``generate`` driven by
         :meth:`prepare_inputs_for_generation`: the full prompt (with audio) once, then one token per step
         against the engine's KV cache; ``stopping_criteria`` are called as ``c(ids, scores)`` each step
@@ -401,22 +403,33 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
         ``length_penalty``, ``early_stopping`` and ``num_return_sequences`` (rows ``[B * num_return_sequences, width]``, best first);
         uniform and padded batches both run on the slot mode, B * num_beams <= 64 slots.  ``return_logprobs`` then gives the returned
         rows' per-token values.  ``share_prefix``: the beams of an example read their prompt once per decode step (off by default).
-        Sampling, a repetition penalty and beam groups are refused under beams.  ``num_beams`` 1 or None: the paths above, unchanged."""
+        Sampling, a repetition penalty and beam groups are refused under beams.  ``num_beams`` 1 or None: the paths above, unchanged.
+
+        ``no_repeat_ngram_size``, ``bad_words_ids``, ``suppress_tokens``, ``min_new_tokens``, ``min_length`` (HF 4.29.2's processors;
+        :mod:`llark_amd.m2t.constraints`): each row's token history -- its own prompt, without the batch's padding, then what it
+        generated -- lives on the device, and one ``ops.constrain_rows`` launch per step sets the banned tokens' logits to -inf before
+        the choice, on every path: greedy, device sampler, ``torch.multinomial``, padded batches and beams.  The ban comes BEFORE the
+        repetition penalty (HF: after); a -inf stays -inf under the penalty and changes no other token, so the distribution is the
+        same.  Under beams the banned tokens still count in the log-softmax and are only left out of the candidates, as in HF.
+        ``min_length`` counts the row's own length.  ``return_logprobs`` stays the model's distribution over the raw logits.  With all
+        of them off (``None``, ``0``, empty) nothing is launched or allocated for them."""
         if num_beam_groups is not None and num_beam_groups != 1:
             raise NotImplementedError(f"num_beam_groups={num_beam_groups!r}: diverse beam groups are not implemented")
+        constraints = constraints_from_generate(no_repeat_ngram_size, bad_words_ids, suppress_tokens, min_new_tokens, min_length)
         if num_beams is not None and num_beams != 1:
             if do_sample:
                 raise NotImplementedError("do_sample=True with num_beams > 1 (beam sampling) is not implemented")
             if repetition_penalty is not None and repetition_penalty != 1.0:
                 raise NotImplementedError("repetition_penalty with num_beams > 1 is not implemented (no logits processors under beams)")
             return self._generate_beam(input_ids, attention_mask, audio_encodings, max_new_tokens, stopping_criteria, eos_token_id,
-                                       num_beams, length_penalty, early_stopping, num_return_sequences, return_logprobs, share_prefix)
+                                       num_beams, length_penalty, early_stopping, num_return_sequences, return_logprobs, share_prefix,
+                                       constraints)
         sampling = params_from_generate(do_sample, temperature, top_k, top_p, repetition_penalty, seed)
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
             return self._generate_ragged(input_ids, attention_mask, audio_encodings, max_new_tokens, do_sample, stopping_criteria,
-                                         eos_token_id, temperature, sampling, return_logprobs)
+                                         eos_token_id, temperature, sampling, return_logprobs, constraints)
         ids = input_ids.to(self.engine.device)
-        sampler = None
+        sampler = cons = None
         eos = eos_token_id if eos_token_id is not None else getattr(self.generation_config, "eos_token_id", None)
         pad = getattr(self.generation_config, "pad_token_id", None)
         pad = eos if pad is None else pad
@@ -441,16 +454,25 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
                 logits = eng.forward_tokens(step_ids, segs, pos0=0, last_only=True)
             past = EngineCache(eng)
             scores = logits[:, -1]
+            chosen_from = scores                                                              # the row the token is chosen from
+            if constraints is not None:
+                if cons is None:
+                    cons = DeviceConstraints(constraints, ids.shape[0], scores.shape[-1], ids.shape[1] + max_new_tokens, ids.device,
+                                             eos_token_id if eos_token_id is not None else getattr(self.generation_config, "eos_token_id", None))
+                    cons.admit(range(ids.shape[0]), list(input_ids))
+                    chosen_from = cons.process(scores)
+                else:
+                    chosen_from = cons.process(scores, last=ids[:, -1])
             if sampling is not None:
                 if sampler is None:
                     sampler = DeviceSampler(sampling, ids.shape[0], scores.shape[-1], ids.device)
                     sampler.admit(range(ids.shape[0]), list(ids), range(ids.shape[0]))
-                nxt = sampler(scores).view(-1, 1)
+                nxt = sampler(chosen_from).view(-1, 1)
             elif do_sample:
-                probs = torch.softmax(scores / max(temperature, 1e-6), dim=-1)
+                probs = torch.softmax(chosen_from / max(temperature, 1e-6), dim=-1)
                 nxt = torch.multinomial(probs, 1)
             else:
-                nxt = scores.argmax(-1, keepdim=True)
+                nxt = chosen_from.argmax(-1, keepdim=True)
             if return_logprobs:                                                               # -1: a finished row has no target
                 lps.append(ops.token_logprob_rows(scores, torch.where(unfinished, nxt, torch.full_like(nxt, -1)).view(-1).contiguous(),
                                                   torch.full((ids.shape[0],), float("nan"), dtype=torch.float32, device=ids.device)))
@@ -462,12 +484,14 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
                 break
             if stopping_criteria is not None and any(bool(c(ids, scores)) for c in stopping_criteria):
                 break
+        if cons is not None:
+            cons.check()
         if return_logprobs:
             return ids, (torch.stack(lps, dim=1) if lps else torch.empty((ids.shape[0], 0), dtype=torch.float32, device=ids.device))
         return ids
 
     def _generate_ragged(self, input_ids, attention_mask, audio_encodings, max_new_tokens, do_sample, stopping_criteria, eos_token_id,
-                         temperature, sampling=None, return_logprobs=False):
+                         temperature, sampling=None, return_logprobs=False, constraints=None):
         """generate() over a padded batch: row b is the sequence input_ids[b][mask[b]] at positions 0 .. len_b - 1 (HF's
         position_ids = cumsum(mask) - 1), one engine slot per row (prefill_slots / decode_slots).  Returns the HF layout: the input
         as given followed by the new tokens; rows that finished emit the pad token."""
@@ -515,6 +539,15 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
 
             def sample(scores):
                 return sampler(scores, state=eng.slot_state)
+        cons = None
+        if constraints is not None:                                                 # the choice, whichever it is, reads the processed rows
+            cons = DeviceConstraints(constraints, B, scores.shape[-1], int(lens.max()) + max_new_tokens, eng.device, eos_k)
+            cons.admit(range(B), rows)
+            constrained = cons.wrap(sample if do_sample else None)
+            do_sample = True
+
+            def sample(scores):
+                return constrained(scores, state=eng.slot_state)
         tracker = None
         if return_logprobs:
             tracker, pick = ragged_logprob_hook(eng, B, scores.shape[-1], max_new_tokens, sample if do_sample else None)
@@ -531,12 +564,14 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
                 break
             nxt, _, scores = eng.decode_slots(nxt, eos_k, pad_k, out[:, S + n], sample if do_sample else None)
             n += 1
+        if cons is not None:
+            cons.check()
         if tracker is not None:
             return out[:, : S + n], ragged_logprob_matrix(tracker, n)
         return out[:, : S + n]
 
     def _generate_beam(self, input_ids, attention_mask, audio_encodings, max_new_tokens, stopping_criteria, eos_token_id, num_beams,
-                       length_penalty, early_stopping, num_return_sequences, return_logprobs, share_prefix):
+                       length_penalty, early_stopping, num_return_sequences, return_logprobs, share_prefix, constraints=None):
         """generate(num_beams > 1): example b is the sequence input_ids[b][mask[b]] (all of it without a mask), prefilled once into
         slot b * num_beams and cloned into the example's other slots; then one engine.beam_step per token.  Returns HF's layout."""
         eng = self.engine
@@ -574,6 +609,10 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
         pad_k = int(pad) if use_eos and pad is not None and pad >= 0 else 0       # the pad token is fed to the embedding: a valid id
         beam = BeamSearch(N, B, scores.shape[-1], max_new_tokens, eng.device, eos if use_eos else None, pad_k, lp, early_stopping)
         beam.admit([int(n) for n in lens])
+        if constraints is not None:                                                # every beam of an example starts from its prompt
+            beam.constraints = DeviceConstraints(constraints, N * B, scores.shape[-1], int(lens.max()) + max_new_tokens, eng.device,
+                                                 eos if use_eos else None)
+            beam.constraints.admit(range(N * B), [rows[s // B] for s in range(N * B)])
         if getattr(self, "beam_observer", None) is not None:                       # tests: install the BeamSearch hooks before the first step
             self.beam_observer(beam, eng)
         scores = scores.repeat_interleave(B, dim=0)
@@ -592,6 +631,8 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
             nxt, done = eng.beam_step(nxt, beam)
             scores = eng._slot_ws["logits"]
             n += 1
+        if beam.constraints is not None:
+            beam.constraints.check()
         ids, lps, _ = beam.finalize(input_ids, max_new_tokens, R)
         return (ids, lps) if return_logprobs else ids
 

@@ -29,6 +29,7 @@ from . import AudioEncoderConfig
 from .llamav2 import EngineCache, plan_audio_splice
 from .logprob import ragged_logprob_hook, ragged_logprob_matrix
 from .mpt_engine import HipMptEngine, MptDims
+from .constraints import DeviceConstraints, constraints_from_generate
 from .sampling import DeviceSampler, params_from_generate
 from .special_tokens import DEFAULT_AUDIO_END_TOKEN, DEFAULT_AUDIO_PATCH_TOKEN, DEFAULT_AUDIO_START_TOKEN
 
@@ -297,7 +298,8 @@ class WrappedMPTForCausalLM(nn.Module):
     def generate(self, input_ids=None, audio_encodings=None, max_new_tokens: int = 20, stopping_criteria=None, eos_token_id=None,
                  attention_mask=None, pad_token_id=None, do_sample: bool = False, temperature: float = 1.0, top_k: Optional[int] = None,
                  top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, seed: Optional[int] = None,
-                 return_logprobs: bool = False, num_beams: Optional[int] = None, **kwargs):
+                 return_logprobs: bool = False, num_beams: Optional[int] = None, no_repeat_ngram_size: Optional[int] = None,
+                 bad_words_ids=None, suppress_tokens=None, min_new_tokens: Optional[int] = None, min_length: Optional[int] = None, **kwargs):
         """Generation loop driven by :meth:`prepare_inputs_for_generation` (prompt with audio once, then one token per step).  An
         ``attention_mask`` with zeros (left- or right-padded) runs every row as if it were alone on the engine's ragged slot mode
         (:meth:`_generate_ragged`); ``None`` or all ones takes this uniform path and never enters the slot mode.
@@ -309,29 +311,45 @@ class WrappedMPTForCausalLM(nn.Module):
         ``return_logprobs``: returns ``(ids, logprobs)``; ``logprobs`` is fp32 ``[B, new tokens]`` on the device, NaN wherever a finished
         row emitted padding (the padded path; the uniform path emits none).  They are log-probabilities of the MODEL's distribution --
         log-softmax of the raw logits, one ``ops.token_logprob_rows`` launch per step; repetition penalty, temperature, top-k and top-p
-        are not applied, for sampled tokens too.  ``num_beams`` > 1 is refused: beam search exists on the Llama engine only."""
+        are not applied, for sampled tokens too.  ``num_beams`` > 1 is refused: beam search exists on the Llama engine only.
+
+        ``no_repeat_ngram_size``, ``bad_words_ids``, ``suppress_tokens``, ``min_new_tokens``, ``min_length`` (HF 4.29.2's processors;
+        :mod:`llark_amd.m2t.constraints`): one ``ops.constrain_rows`` launch per step sets the banned tokens' logits to -inf before the
+        choice, greedy or sampled, uniform or padded, from each row's history on the device (its own prompt without padding, then what
+        it generated).  The ban comes BEFORE the repetition penalty (HF: after): a -inf stays -inf under the penalty and changes no
+        other token, so the distribution is the same.  ``min_length`` counts the row's own length; ``return_logprobs`` stays the
+        model's distribution over the raw logits.  All off (``None``, ``0``, empty): nothing is launched or allocated for them."""
         if num_beams is not None and num_beams != 1:
             raise NotImplementedError(f"num_beams={num_beams!r}: beam search is not implemented for MPT (no K/V fork path there yet)")
+        constraints = constraints_from_generate(no_repeat_ngram_size, bad_words_ids, suppress_tokens, min_new_tokens, min_length)
         sampling = params_from_generate(do_sample, temperature, top_k, top_p, repetition_penalty, seed, always=bool(do_sample))
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
             return self._generate_ragged(input_ids, attention_mask, audio_encodings, max_new_tokens, stopping_criteria, eos_token_id,
-                                         pad_token_id, sampling, return_logprobs)
+                                         pad_token_id, sampling, return_logprobs, constraints)
         ids = input_ids.to(self.engine.device)
         past = None
-        sampler = None
+        sampler = cons = None
         lps = []
         for _ in range(max_new_tokens):
             inp = self.prepare_inputs_for_generation(ids, past_key_values=past, audio_encodings=audio_encodings)
             out = self.forward(inp["input_ids"], past_key_values=inp["past_key_values"], audio_encodings=inp["audio_encodings"])
             past = out.past_key_values
             scores = out.logits[:, -1]
+            chosen_from = scores                                                              # the row the token is chosen from
+            if constraints is not None:
+                if cons is None:
+                    cons = DeviceConstraints(constraints, ids.shape[0], scores.shape[-1], ids.shape[1] + max_new_tokens, ids.device, eos_token_id)
+                    cons.admit(range(ids.shape[0]), list(input_ids))
+                    chosen_from = cons.process(scores)
+                else:
+                    chosen_from = cons.process(scores, last=ids[:, -1])
             if sampling is not None:
                 if sampler is None:
                     sampler = DeviceSampler(sampling, ids.shape[0], scores.shape[-1], ids.device)
                     sampler.admit(range(ids.shape[0]), list(ids), range(ids.shape[0]))
-                nxt = sampler(scores).view(-1, 1)
+                nxt = sampler(chosen_from).view(-1, 1)
             else:
-                nxt = scores.argmax(-1, keepdim=True)
+                nxt = chosen_from.argmax(-1, keepdim=True)
             if return_logprobs:
                 lps.append(ops.token_logprob_rows(scores, nxt.view(-1).contiguous(),
                                                   torch.full((ids.shape[0],), float("nan"), dtype=torch.float32, device=ids.device)))
@@ -340,12 +358,14 @@ class WrappedMPTForCausalLM(nn.Module):
                 break
             if stopping_criteria is not None and any(bool(c(ids, scores)) for c in stopping_criteria):
                 break
+        if cons is not None:
+            cons.check()
         if return_logprobs:
             return ids, (torch.stack(lps, dim=1) if lps else torch.empty((ids.shape[0], 0), dtype=torch.float32, device=ids.device))
         return ids
 
     def _generate_ragged(self, input_ids, attention_mask, audio_encodings, max_new_tokens, stopping_criteria, eos_token_id, pad_token_id,
-                         sampling=None, return_logprobs=False):
+                         sampling=None, return_logprobs=False, constraints=None):
         """generate() over a padded batch (``WrappedLlamav2ForCausalLM._generate_ragged``): row b is the sequence
         input_ids[b][mask[b]] at positions 0 .. len_b - 1, one engine slot per row (prefill_slots / decode_slots).  Returns the HF
         layout: the input as given followed by the new tokens; a row that emitted EOS continues with the pad token (EOS when none)."""
@@ -383,6 +403,14 @@ class WrappedMPTForCausalLM(nn.Module):
 
             def sample(scores):
                 return sampler(scores, state=eng.slot_state)
+        cons = None
+        if constraints is not None:                                                 # the choice, whichever it is, reads the processed rows
+            cons = DeviceConstraints(constraints, B, scores.shape[-1], int(lens.max()) + max_new_tokens, eng.device, eos_k)
+            cons.admit(range(B), rows)
+            constrained = cons.wrap(sample)
+
+            def sample(scores):
+                return constrained(scores, state=eng.slot_state)
         tracker = None
         if return_logprobs:
             tracker, sample = ragged_logprob_hook(eng, B, scores.shape[-1], max_new_tokens, sample)
@@ -397,6 +425,8 @@ class WrappedMPTForCausalLM(nn.Module):
                 break
             nxt, _, scores = eng.decode_slots(nxt, eos_k, pad_k, out[:, S + n], sample)
             n += 1
+        if cons is not None:
+            cons.check()
         if tracker is not None:
             return out[:, : S + n], ragged_logprob_matrix(tracker, n)
         return out[:, : S + n]

@@ -1199,11 +1199,14 @@ BEAM_META_STRIDE = 4                  # int32 per example: count, worst score f3
 
 def beam_topk_rows(logits: torch.Tensor, score: torch.Tensor, beams: int, cand_score: torch.Tensor, cand_token: torch.Tensor,
                    cand_logprob: torch.Tensor, *, vocab: Optional[int] = None, state: Optional[torch.Tensor] = None,
-                   slot_of_row: Optional[torch.Tensor] = None, fallbacks: Optional[torch.Tensor] = None) -> None:
+                   slot_of_row: Optional[torch.Tensor] = None, fallbacks: Optional[torch.Tensor] = None,
+                   ban: Optional[torch.Tensor] = None) -> None:
     """The 2 * ``beams`` best candidates ``fp32(score[slot] + log_softmax(row)[t])`` of every row of fp32 ``logits`` [rows, >= vocab], sorted
     by candidate descending, then token ascending, into ``cand_score`` / ``cand_token`` (int32) / ``cand_logprob`` [rows, 2 * beams]; the
     log-probabilities are bit-equal to :func:`token_logprob_rows`.  ``score`` fp32 [slots]; rows of slots that are not ROW_ACTIVE (with
-    ``state``) are skipped.  Contract: include/llark_hip.h (llark_beam_topk_rows)."""
+    ``state``) are skipped.  ``ban`` (int32 [slots, >= ceil(vocab / 32)], the bitmap of :func:`constrain_rows`): banned tokens are left
+    out of the selection and still count in the log-softmax (llark_beam_topk_rows_banned).  Contract: include/llark_hip.h
+    (llark_beam_topk_rows)."""
     i32, f32 = torch.int32, torch.float32
     assert logits.dim() == 2 and logits.stride(1) == 1
     rows = logits.shape[0]
@@ -1211,10 +1214,70 @@ def beam_topk_rows(logits: torch.Tensor, score: torch.Tensor, beams: int, cand_s
     slots = score.numel()
     assert 0 < vocab <= logits.shape[1] and (state is None or state.numel() == slots) and (slot_of_row is None or slot_of_row.numel() == rows)
     assert all(t.numel() == rows * 2 * beams for t in (cand_score, cand_token, cand_logprob))
+    if ban is not None:
+        assert ban.dim() == 2 and ban.shape[0] == slots and ban.stride(1) == 1 and ban.shape[1] >= (vocab + 31) // 32
+        check(_lib.lib().llark_beam_topk_rows_banned(_dev(logits, "logits", f32, contiguous=False), logits.stride(0), vocab, rows, slots,
+                                                     _opt(state, "state", i32), _opt(slot_of_row, "slot_of_row", i32),
+                                                     _dev(score, "score", f32), int(beams), _dev(cand_score, "cand_score", f32),
+                                                     _dev(cand_token, "cand_token", i32), _dev(cand_logprob, "cand_logprob", f32),
+                                                     _opt(fallbacks, "fallbacks", i32), _dev(ban, "ban", i32, contiguous=False),
+                                                     ban.stride(0), _stream()), "beam_topk_rows_banned")
+        return
     check(_lib.lib().llark_beam_topk_rows(_dev(logits, "logits", f32, contiguous=False), logits.stride(0), vocab, rows, slots,
                                           _opt(state, "state", i32), _opt(slot_of_row, "slot_of_row", i32), _dev(score, "score", f32),
                                           int(beams), _dev(cand_score, "cand_score", f32), _dev(cand_token, "cand_token", i32),
                                           _dev(cand_logprob, "cand_logprob", f32), _opt(fallbacks, "fallbacks", i32), _stream()), "beam_topk_rows")
+
+
+CONSTRAIN_MAX_VOCAB = 65536           # caps of llark_constrain_rows (csrc/constrain.hip)
+CONSTRAIN_MAX_NGRAM = 64
+CONSTRAIN_MAX_WORDS = 4096
+CONSTRAIN_MAX_WORD_TOKENS = 1 << 20
+CONSTRAIN_STATUS_FULL = 1             # bit 0 of the status word: a history row was full, a token was not appended
+
+
+def constrain_rows(logits: torch.Tensor, *, vocab: Optional[int] = None, state: Optional[torch.Tensor] = None,
+                   slot_of_row: Optional[torch.Tensor] = None, hist: Optional[torch.Tensor] = None, hist_len: Optional[torch.Tensor] = None,
+                   prompt_len: Optional[torch.Tensor] = None, parent: Optional[torch.Tensor] = None, last_token: Optional[torch.Tensor] = None,
+                   no_repeat_ngram_size: int = 0, bw_tokens: Optional[torch.Tensor] = None, bw_off: Optional[torch.Tensor] = None,
+                   eos: int = -1, min_new_tokens: int = 0, min_length: int = 0, out: Optional[torch.Tensor] = None,
+                   ban: Optional[torch.Tensor] = None, n_banned: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None,
+                   slots: Optional[int] = None) -> None:
+    """The tokens banned for the next choice of every row of fp32 ``logits`` [rows, >= vocab], in one launch: HF 4.29.2's
+    ``no_repeat_ngram_size``, bad words (``bw_tokens`` int32 flat, ``bw_off`` int32 [words + 1]) and the ``min_new_tokens`` / ``min_length``
+    ban on ``eos``, over the slot's history ``hist`` (int32 [slots, width]) / ``hist_len`` / ``prompt_len`` (int32 [slots]).  Before the
+    bans the history is brought up to date: a slot whose ``parent`` entry (int32 [slots], any element stride) names another slot takes
+    that slot's row, then ``last_token[slot]`` (int64 [slots]) is appended.  ``out`` (fp32 [rows, >= vocab]) receives the row with -inf
+    at the banned columns, ``ban`` (int32 [slots, >= ceil(vocab / 32)]) the bitmap, ``n_banned`` (int32 [rows]) the count; a full
+    history row sets CONSTRAIN_STATUS_FULL in ``status`` (int32 [1]).  Row r belongs to slot ``slot_of_row[r]`` (identity without it);
+    with ``state`` only ROW_ACTIVE slots are touched.  Contract: include/llark_hip.h (llark_constrain_rows)."""
+    i32, f32 = torch.int32, torch.float32
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    rows = logits.shape[0]
+    vocab = logits.shape[1] if vocab is None else int(vocab)
+    assert 0 < vocab <= logits.shape[1]
+    per_slot = [t for t in (state, hist_len, prompt_len, last_token) if t is not None]
+    if slots is None:
+        slots = hist.shape[0] if hist is not None else ban.shape[0] if ban is not None else per_slot[0].numel() if per_slot else rows
+    assert all(t.numel() == slots for t in per_slot)
+    assert hist is None or (hist.dim() == 2 and hist.shape[0] == slots and hist.is_contiguous())
+    assert parent is None or (parent.dim() == 1 and parent.shape[0] == slots)
+    assert ban is None or (ban.dim() == 2 and ban.shape[0] == slots and ban.stride(1) == 1)
+    assert out is None or (out.dim() == 2 and out.shape[0] == rows and out.stride(1) == 1 and out.shape[1] >= vocab)
+    assert all(t is None or t.numel() == rows for t in (slot_of_row, n_banned)) and (status is None or status.numel() == 1)
+    n_words = 0 if bw_off is None else bw_off.numel() - 1
+    assert n_words >= 0 and (n_words == 0 or bw_tokens is not None)
+    check(_lib.lib().llark_constrain_rows(_dev(logits, "logits", f32, contiguous=False), logits.stride(0), vocab, rows, int(slots),
+                                          _opt(state, "state", i32), _opt(slot_of_row, "slot_of_row", i32), _opt(hist, "hist", i32),
+                                          hist.shape[1] if hist is not None else 0, _opt(hist_len, "hist_len", i32),
+                                          _opt(prompt_len, "prompt_len", i32), _opt(parent, "parent", i32, contiguous=False),
+                                          parent.stride(0) if parent is not None else 1, _opt(last_token, "last_token", torch.int64),
+                                          int(no_repeat_ngram_size), _opt(bw_tokens, "bw_tokens", i32) if n_words else None,
+                                          _opt(bw_off, "bw_off", i32) if n_words else None, n_words,
+                                          bw_tokens.numel() if n_words else 0, int(eos), int(min_new_tokens), int(min_length),
+                                          _opt(out, "out", f32, contiguous=False), _ld(out), _opt(ban, "ban", i32, contiguous=False),
+                                          _ld(ban), _opt(n_banned, "n_banned", i32), _opt(status, "status", i32), _stream()),
+          "constrain_rows")
 
 
 def beam_advance(cand_score: torch.Tensor, cand_token: torch.Tensor, cand_logprob: torch.Tensor, n_examples: int, beams: int, step: int,

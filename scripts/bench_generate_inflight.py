@@ -32,6 +32,12 @@ step's excess as a fraction of the greedy step.  ONE JSON line.
 Greedy against greedy + token log-probabilities, same run and same block scheme: the second kind's step picks its token with
 ops.sample_rows(do_sample=False) and appends its log-probability to the slot's history (ops.token_logprob_rows), two more launches per
 step, as EngineSlots(logprobs=True) does.  ONE JSON line, also written to --out.
+
+    python scripts/bench_generate_inflight.py --constraints [--slots 16,64] [--out profiles/bench_generate_inflight_constraints.json]
+Greedy against constrained greedy, same run and same block scheme: the second kind's step turns its logits into the processed rows
+(ops.constrain_rows under no_repeat_ngram_size 3, two bad words and min_new_tokens; the histories live on the device) and picks its
+token from them with ops.sample_rows(do_sample=False), two more launches per step, as EngineSlots(constraints=...) does.  ONE JSON line,
+also written to --out.
 """
 import argparse
 import json
@@ -366,13 +372,70 @@ def main_logprobs(args, slot_list):
     print(json.dumps(res), flush=True)
 
 
+def main_constraints(args, slot_list):
+    import statistics
+
+    from llark_amd.m2t.constraints import DeviceConstraints, TokenConstraints
+    steps, blocks = 16, 8
+    examples = make_examples(64, args.seed)
+    max_seq = max(ids.numel() for ids, _, _ in examples) + 8 + steps * (2 * blocks + 2)
+    model = RandomLlama(args.precision, max(slot_list), max_seq)
+    eng = model.engine
+    tc = TokenConstraints(no_repeat_ngram_size=3, bad_words_ids=[[5], [6, 7]], min_new_tokens=8)
+    res = {"bench": "generate_inflight_constraints", "model": "llama2-7b dims, random weights", "precision": args.precision,
+           "constraints": dict(no_repeat_ngram_size=3, bad_words=2, min_new_tokens=8, eos=2), "steps_per_block": steps, "blocks": blocks, "slots": {}}
+    for n in slot_list:
+        eng.init_slots(n)
+        rows = [examples[i % len(examples)] for i in range(n)]
+        logits = eng.prefill_slots([r[0].cuda() for r in rows], [(k, 1, r[1].cuda()) for k, r in enumerate(rows)], range(n))
+        cons = DeviceConstraints(tc, n, logits.shape[-1], eng.smax + 1, eng.device, eos=2)
+        cons.admit(range(n), [r[0] for r in rows])
+        constrained = cons.wrap(None)                            # greedy on the processed rows: one constrain_rows + one sample_rows launch
+        kinds = {"greedy": None, "constrained": lambda lg: constrained(lg, state=eng.slot_state)}
+        ids = constrained(logits, state=eng.slot_state)
+
+        def block(kind):
+            nonlocal ids
+            if kind == "constrained":
+                cons.remember(ids)                               # the tokens the last step, of either kind, handed out
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                ids, _, _ = eng.decode_slots(ids, sample=kinds[kind])
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / steps * 1e3
+
+        block("greedy"), block("constrained")                    # warm
+        ms = {"greedy": [], "constrained": []}
+        for b in range(blocks):
+            for kind in (("greedy", "constrained") if b % 2 == 0 else ("constrained", "greedy")):
+                ms[kind].append(block(kind))
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        assert not cons.full() and int(cons.hist_len.min()) >= steps * (blocks + 1)
+        cell = {"greedy_step_ms": round(med["greedy"], 4), "constrained_step_ms": round(med["constrained"], 4),
+                "greedy_min_max_ms": [round(min(ms["greedy"]), 4), round(max(ms["greedy"]), 4)],
+                "constrained_min_max_ms": [round(min(ms["constrained"]), 4), round(max(ms["constrained"]), 4)],
+                "excess_fraction_of_step": round(med["constrained"] / med["greedy"] - 1.0, 4)}
+        res["slots"][str(n)] = cell
+        print(json.dumps({str(n): cell}), file=sys.stderr, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--constraints", action="store_true", help="same-run A/B of the decode step with every slot active: greedy against greedy "
+                    "under no_repeat_ngram_size 3, two bad words and min_new_tokens (default slot counts 16,64)")
     ap.add_argument("--sampling", action="store_true", help="same-run A/B of the decode step with every slot active: greedy against the "
                     "device sampler (default slot counts 16,64)")
     ap.add_argument("--logprobs", action="store_true", help="same-run A/B of the decode step with every slot active: greedy against greedy + "
                     "token log-probabilities (default slot counts 16,64)")
-    ap.add_argument("--out", default=None, help="with --logprobs: also write the JSON here (default profiles/bench_generate_inflight_logprobs.json)")
+    ap.add_argument("--out", default=None, help="with --logprobs / --constraints: also write the JSON here (default "
+                    "profiles/bench_generate_inflight_logprobs.json / profiles/bench_generate_inflight_constraints.json)")
     ap.add_argument("--questions-per-clip", default=None, help="e.g. 1,4,8: consecutive examples share an encoding, an audio-first prefix "
                     "and a prefix key (inflight schedule only; one result cell per slot count and value)")
     ap.add_argument("--share-prefix", action="store_true", help="with --questions-per-clip: run every cell with share_prefix off and on")
@@ -393,6 +456,10 @@ def main():
         if args.out is None:
             args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "bench_generate_inflight_logprobs.json")
         return main_logprobs(args, [16, 64] if args.slots == ap.get_default("slots") else slot_list)
+    if args.constraints:
+        if args.out is None:
+            args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "bench_generate_inflight_constraints.json")
+        return main_constraints(args, [16, 64] if args.slots == ap.get_default("slots") else slot_list)
     if args.questions_per_clip:
         return main_shared(args, slot_list)
     if args.share_prefix:
