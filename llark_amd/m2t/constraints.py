@@ -108,7 +108,6 @@ class DeviceConstraints:
         self.out = torch.zeros((n_slots, vocab), dtype=torch.float32, device=self.device)    # zeros: a skipped row stays a valid row
         self.ban = None                                            # beams only: built at the first process(bitmap=True)
         self.status = torch.zeros((1,), **i32)
-        self.last = torch.zeros((n_slots,), dtype=torch.int64, device=self.device)      # per slot: the token wrap()'s callable handed out last
 
     def _slots(self, slots: Sequence[int], what: str):
         slots = [int(b) for b in slots]
@@ -168,38 +167,6 @@ class DeviceConstraints:
         out = self.out[:rows]
         ops.constrain_rows(logits, out=out, **kw)
         return out
-
-    def remember(self, tokens: torch.Tensor, slot_of_row=None) -> None:
-        """The tokens just handed out (int64 [rows]), kept per slot: the next ``process`` appends them."""
-        tokens = tokens.reshape(-1).to(torch.int64)
-        if slot_of_row is None:
-            self.last[: tokens.numel()] = tokens
-        else:
-            self.last[torch.as_tensor(slot_of_row, dtype=torch.long, device=self.device)] = tokens
-
-    def wrap(self, choose=None):
-        """``choose`` (``logits -> tokens``, e.g. a :class:`DeviceSampler`) -> ``constrained(logits, state=None, slot_of_row=None) ->
-        tokens``, for callers that only see ``logits -> tokens``: the choice is made on the processed rows and remembered per slot, and
-        the next call appends it.  The callable's first call, and every call with a ``slot_of_row`` (a refill's prefill), are prefill
-        rows: nothing is appended.  None: the advance kernel's own first-maximum rule."""
-        started = [False]
-
-        def greedy(rows, state=None, slot_of_row=None):
-            return ops.sample_rows(rows, torch.zeros((rows.shape[0],), dtype=torch.int64, device=rows.device), vocab=self.vocab, state=state,
-                                   slot_of_row=slot_of_row, do_sample=False, repetition_penalty=1.0, slots=self.n_slots)
-
-        def constrained(logits, state=None, slot_of_row=None):
-            prefill = slot_of_row is not None or not started[0]
-            started[0] = True
-            rows = self.process(logits, state=state, slot_of_row=slot_of_row, last=None if prefill else self.last)
-            if choose is not None:
-                tokens = choose(rows)                              # a callable of the rows alone: it knows its own state
-            else:
-                sor = None if slot_of_row is None else torch.as_tensor(slot_of_row, dtype=torch.int32, device=self.device)
-                tokens = greedy(rows, state=state, slot_of_row=sor)
-            self.remember(tokens, slot_of_row)
-            return tokens
-        return constrained
 
     def check(self) -> None:
         """Raises when a history row was full (:meth:`full`): from then on the bans were computed from a history that lacks tokens."""

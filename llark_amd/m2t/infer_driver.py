@@ -283,7 +283,8 @@ class EngineSlots:
     (:class:`llark_amd.m2t.logprob.LogprobTracker`, one launch per step); ``take_logprobs(slots)`` reads finished slots' histories.
     ``constraints`` (a :class:`llark_amd.m2t.constraints.TokenConstraints`): every choice, greedy or sampled, is made on the logits with
     -inf at the tokens its example's history bans (one more launch per step, no transfer); the EOS of ``min_new_tokens`` /
-    ``min_length`` is the model's ``generation_config.eos_token_id``."""
+    ``min_length`` is the model's ``generation_config.eos_token_id``.  The stages that are on run in the order of one
+    :class:`llark_amd.m2t.choice.TokenChooser`."""
 
     def __init__(self, model, n_slots: int, share_prefix: bool = False, sampling=None, logprobs: bool = False, constraints=None):
         from .llamav2 import plan_audio_splice
@@ -296,13 +297,12 @@ class EngineSlots:
             self.eng.init_slots(n_slots, share_prefix=True)
         else:
             self.eng.init_slots(n_slots)
+        self.n_slots = n_slots
         self.ids = torch.zeros((n_slots,), dtype=torch.int64, device=self.eng.device)
-        self.sampling = sampling if sampling is not None and sampling.active else None
-        self.sampler = None                                       # built at the first prefill, which tells the logits' width
-        self.logprobs = bool(logprobs)
-        self.tracker = None                                       # likewise
-        self.constraints = constraints if constraints is not None and constraints.active else None
-        self.cons = None                                          # likewise
+        stages = dict(sampling=sampling if sampling is not None and sampling.active else None,
+                      constraints=constraints if constraints is not None and constraints.active else None, logprobs=bool(logprobs))
+        self.stages = stages if any(stages.values()) else None    # None: plain greedy calls, nothing launched or allocated
+        self.chooser = None                                       # built at the first prefill, which tells the logits' width
         cfg = model.get_model().audio_encoder_config
         self.audio_token_ids = tuple(int(t) for t in (getattr(cfg, name, None) for name in ("audio_start_token", "audio_end_token", "audio_patch_token"))
                                      if t is not None)
@@ -322,67 +322,36 @@ class EngineSlots:
             logits = eng.prefill_slots([p.to(eng.device) for p in prompts], segs, slots)
         else:
             logits = eng.prefill_slots([p.to(eng.device) for p in prompts], segs, slots, past=past)
-        raw = logits
-        if self.constraints is not None:
-            if self.cons is None:
-                from .constraints import DeviceConstraints
-
-                eos = getattr(getattr(self.model, "generation_config", None), "eos_token_id", None)
-                # a history is at most the cache's smax positions plus the token just chosen: the engine refuses a slot beyond smax first
-                self.cons = DeviceConstraints(self.constraints, eng.n_slots, logits.shape[-1], eng.smax + 1, eng.device, eos)
-            self.cons.admit(slots, prompts if whole is None else whole)
-            logits = self.cons.process(raw, state=eng.slot_state, slot_of_row=list(slots))
-        if self.sampling is not None:
-            if self.sampler is None:
-                from .sampling import DeviceSampler
-
-                self.sampler = DeviceSampler(self.sampling, eng.n_slots, logits.shape[-1], eng.device)
-            self.sampler.admit(slots, prompts if whole is None else whole, slots if indices is None else indices)
-            first = self.sampler(logits, state=eng.slot_state, slot_of_row=list(slots))
-        else:
+        if self.stages is None:
             first = logits.argmax(-1)                              # what generate() picks after the prompt
-        logits = raw                                               # log-probabilities: the model's own distribution
-        if self.logprobs:
-            if self.tracker is None:
-                from .logprob import LogprobTracker
+        else:
+            if self.chooser is None:
+                from .choice import TokenChooser
 
-                self.tracker = LogprobTracker(eng.n_slots, logits.shape[-1], eng.device, eng.smax)
-            self.tracker.admit(slots)
-            self.tracker(logits, first, state=eng.slot_state, slot_of_row=list(slots))
+                # a history is at most the cache's smax positions plus the token just chosen: the engine refuses a slot beyond smax first
+                self.chooser = TokenChooser(self.n_slots, logits.shape[-1], eng.device, history_len=eng.smax + 1, logprob_width=eng.smax,
+                                            eos=getattr(getattr(self.model, "generation_config", None), "eos_token_id", None), **self.stages)
+            self.chooser.admit(slots, prompts if whole is None else whole, indices)
+            first = self.chooser(logits, state=eng.slot_state, slot_of_row=list(slots))
         self.ids[torch.tensor(slots, dtype=torch.long, device=eng.device)] = first
         return first.cpu().tolist()
 
     def decode(self):
-        if self.sampler is not None or self.tracker is not None or self.cons is not None:
-            self.ids, host, _ = self.eng.decode_slots(self.ids, sample=self._sample)
+        if self.chooser is not None:
+            self.ids, host, _ = self.eng.decode_slots(self.ids, sample=lambda lg: self.chooser(lg, state=self.eng.slot_state))
         else:
             self.ids, host, _ = self.eng.decode_slots(self.ids)
         return host.tolist()
 
-    def _sample(self, logits):
-        rows = logits if self.cons is None else self.cons.process(logits, state=self.eng.slot_state, last=self.ids)
-        if self.sampler is not None:
-            tokens = self.sampler(rows, state=self.eng.slot_state)
-        else:                                                      # the advance kernel's own rule: the first maximal index
-            from .. import ops
-
-            tokens = ops.sample_rows(rows, torch.zeros((rows.shape[0],), dtype=torch.int64, device=rows.device),
-                                     state=self.eng.slot_state, do_sample=False, repetition_penalty=1.0)
-        if self.tracker is not None:
-            self.tracker(logits, tokens, state=self.eng.slot_state)
-        return tokens
-
     def take_logprobs(self, slots):
-        if self.tracker is None:
+        if self.stages is None or not self.stages["logprobs"]:
             raise RuntimeError("EngineSlots: built without logprobs=True")
-        return self.tracker.take(slots)
+        return self.chooser.take_logprobs(slots)
 
     def release(self, slots):
         self.eng.release_slots(slots)
-        if self.sampler is not None:
-            self.sampler.release(slots)
-        if self.cons is not None:
-            self.cons.release(slots)
+        if self.chooser is not None:
+            self.chooser.release(slots)
 
 
 @torch.no_grad()

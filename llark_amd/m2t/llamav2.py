@@ -26,10 +26,10 @@ from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutpu
 from .. import ops
 from . import AudioEncoderConfig
 from .beam import BeamSearch, check_beam_args
+from .choice import TokenChooser, generate_padded, unpack_prompts
 from .constraints import DeviceConstraints, constraints_from_generate
 from .engine import HipLlamaEngine, LlamaDims
-from .logprob import ragged_logprob_hook, ragged_logprob_matrix
-from .sampling import DeviceSampler, params_from_generate
+from .sampling import params_from_generate
 from .special_tokens import DEFAULT_AUDIO_END_TOKEN, DEFAULT_AUDIO_PATCH_TOKEN, DEFAULT_AUDIO_START_TOKEN
 
 
@@ -115,6 +115,18 @@ def _plan_patch_splice(input_ids, audio_features, cfg: AudioEncoderConfig) -> Li
             raise ValueError("The image patch tokens should be consecutive.")
         segs.append((b, first - 1, feats))
     return segs
+
+
+def plan_splice_on(device, input_ids, audio_encodings, cfg: AudioEncoderConfig, has_past: bool = False,
+                   patch_branch: bool = False) -> List[Tuple[int, int, torch.Tensor]]:
+    """The features (a tensor or a list of them) to ``device`` as fp32, then :func:`plan_audio_splice`; None: no segments."""
+    if audio_encodings is None:
+        return []
+    if isinstance(audio_encodings, (list, tuple)):
+        feats = [f.to(device=device, dtype=torch.float32) for f in audio_encodings]
+    else:
+        feats = audio_encodings.to(device=device, dtype=torch.float32)
+    return plan_audio_splice(input_ids, feats, cfg, has_past, patch_branch=patch_branch)
 
 
 class _HipTrainStep(torch.autograd.Function):
@@ -283,15 +295,7 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
         has_past = bool(past_key_values) if past_key_values is not None else False
         pos0 = eng.cur_len if has_past else 0
         cfg = self.model.audio_encoder_config
-        feats = audio_encodings
-        if feats is not None and getattr(self.config, "use_mm_proj", False):
-            if isinstance(feats, (list, tuple)):
-                feats = [f.to(device=eng.device, dtype=torch.float32) for f in feats]
-            else:
-                feats = feats.to(device=eng.device, dtype=torch.float32)
-            segs = plan_audio_splice(input_ids, feats, cfg, has_past)
-        else:
-            segs = []
+        segs = plan_splice_on(eng.device, input_ids, audio_encodings, cfg, has_past) if getattr(self.config, "use_mm_proj", False) else []
         hidden = [] if output_hidden_states else None      # HF layout: the stream entering every layer, then norm(last) -- (L + 1) x (B, S, H)
         logits = eng.forward_tokens(input_ids, segs, pos0=pos0, hidden_sink=hidden)
         loss = None
@@ -345,13 +349,10 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
             copy_weights_into_engine(eng, self.state_dict(), origin="module parameters")
         self._engine = None                                     # the inference engine is rebuilt lazily in its own mode
         input_ids = input_ids.to(eng.device)
-        feats = audio_encodings
         segs = []
-        if feats is not None and getattr(self.config, "use_mm_proj", False):
-            feats = [f.to(device=eng.device, dtype=torch.float32) for f in feats] if isinstance(feats, (list, tuple)) \
-                else feats.to(device=eng.device, dtype=torch.float32)
-            segs = plan_audio_splice(input_ids, feats, self.model.audio_encoder_config, False)
-        named = [(n, p) for n, p in self.named_parameters() if p.requires_grad]
+        if getattr(self.config, "use_mm_proj", False):
+            segs = plan_splice_on(eng.device, input_ids, audio_encodings, self.model.audio_encoder_config)
+        named =[(n, p) for n, p in self.named_parameters() if p.requires_grad]
         names = [n for n, _ in named]
         loss = _HipTrainStep.apply(self, input_ids, segs, labels.to(eng.device), names, *[p for _, p in named])
         if return_dict is False:
@@ -387,7 +388,7 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
         against the engine's KV cache; ``stopping_criteria`` are called as ``c(ids, scores)`` each step
         (m2t/generate.py:31-44, m2t/infer.py:146-152).  An ``attention_mask`` with zeros (left-padded, the HF convention for
         batched decoder-only generation, or right-padded) runs every row as if it were alone on the engine's ragged slot mode
-        (:meth:`_generate_ragged`); ``None`` or all ones takes this uniform path.
+        (:func:`llark_amd.m2t.choice.generate_padded`); ``None`` or all ones takes this uniform path.
 
         ``do_sample`` with ``temperature`` alone draws with ``torch.multinomial`` from torch's global generator, as ever.  Any of
         ``top_k`` / ``top_p`` / ``repetition_penalty`` / ``seed`` moves the token choice to the device sampler
@@ -425,150 +426,57 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
                                        num_beams, length_penalty, early_stopping, num_return_sequences, return_logprobs, share_prefix,
                                        constraints)
         sampling = params_from_generate(do_sample, temperature, top_k, top_p, repetition_penalty, seed)
-        if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
-            return self._generate_ragged(input_ids, attention_mask, audio_encodings, max_new_tokens, do_sample, stopping_criteria,
-                                         eos_token_id, temperature, sampling, return_logprobs, constraints)
-        ids = input_ids.to(self.engine.device)
-        sampler = cons = None
+        eng = self.engine
         eos = eos_token_id if eos_token_id is not None else getattr(self.generation_config, "eos_token_id", None)
         pad = getattr(self.generation_config, "pad_token_id", None)
         pad = eos if pad is None else pad
+        use_eos = eos is not None and eos >= 0
+
+        def draw(rows):
+            return torch.multinomial(torch.softmax(rows / max(temperature, 1e-6), dim=-1), 1)
+        choose = draw if do_sample and sampling is None else None                             # do_sample with temperature alone
+        if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
+            rows, _, packed = unpack_prompts(input_ids, attention_mask)
+            segs = plan_splice_on(eng.device, packed, audio_encodings, self.model.audio_encoder_config)
+            return generate_padded(eng, rows, segs, input_ids, *((int(eos), int(pad)) if use_eos else (-1, 0)), max_new_tokens,
+                                   stopping_criteria, sampling=sampling, constraints=constraints, return_logprobs=return_logprobs,
+                                   choose=choose)
+        choose = choose or (lambda rows: rows.argmax(-1, keepdim=True))
+        ids = input_ids.to(eng.device)
+        chooser = TokenChooser.build(ids.shape[0], eng.dims.vocab_size, ids.device, sampling=sampling, constraints=constraints,
+                                     history_len=ids.shape[1] + max_new_tokens, eos=eos, choose=choose)
+        if chooser is not None:
+            chooser.admit(range(ids.shape[0]), list(input_ids))
         unfinished = torch.ones((ids.shape[0], 1), dtype=torch.bool, device=ids.device)      # HF: unfinished_sequences, per row
         past = None
         lps = []
         for _ in range(max_new_tokens):
             inputs = self.prepare_inputs_for_generation(ids, past_key_values=past, audio_encodings=audio_encodings)
-            eng = self.engine
             step_ids = inputs["input_ids"]
             if past:
                 logits = eng.forward_tokens(step_ids, (), pos0=eng.cur_len, last_only=True)
             else:
-                feats = inputs["audio_encodings"]
-                segs = []
-                if feats is not None:
-                    if isinstance(feats, (list, tuple)):
-                        feats = [f.to(device=eng.device, dtype=torch.float32) for f in feats]
-                    else:
-                        feats = feats.to(device=eng.device, dtype=torch.float32)
-                    segs = plan_audio_splice(step_ids, feats, self.model.audio_encoder_config, False)
+                segs = plan_splice_on(eng.device, step_ids, inputs["audio_encodings"], self.model.audio_encoder_config)
                 logits = eng.forward_tokens(step_ids, segs, pos0=0, last_only=True)
             past = EngineCache(eng)
             scores = logits[:, -1]
-            chosen_from = scores                                                              # the row the token is chosen from
-            if constraints is not None:
-                if cons is None:
-                    cons = DeviceConstraints(constraints, ids.shape[0], scores.shape[-1], ids.shape[1] + max_new_tokens, ids.device,
-                                             eos_token_id if eos_token_id is not None else getattr(self.generation_config, "eos_token_id", None))
-                    cons.admit(range(ids.shape[0]), list(input_ids))
-                    chosen_from = cons.process(scores)
-                else:
-                    chosen_from = cons.process(scores, last=ids[:, -1])
-            if sampling is not None:
-                if sampler is None:
-                    sampler = DeviceSampler(sampling, ids.shape[0], scores.shape[-1], ids.device)
-                    sampler.admit(range(ids.shape[0]), list(ids), range(ids.shape[0]))
-                nxt = sampler(chosen_from).view(-1, 1)
-            elif do_sample:
-                probs = torch.softmax(chosen_from / max(temperature, 1e-6), dim=-1)
-                nxt = torch.multinomial(probs, 1)
-            else:
-                nxt = chosen_from.argmax(-1, keepdim=True)
+            nxt = (choose if chooser is None else chooser)(scores).view(-1, 1)
             if return_logprobs:                                                               # -1: a finished row has no target
                 lps.append(ops.token_logprob_rows(scores, torch.where(unfinished, nxt, torch.full_like(nxt, -1)).view(-1).contiguous(),
                                                   torch.full((ids.shape[0],), float("nan"), dtype=torch.float32, device=ids.device)))
-            if eos is not None and eos >= 0:
+            if use_eos:
                 nxt = torch.where(unfinished, nxt, torch.full_like(nxt, pad))                 # finished rows emit padding
                 unfinished = unfinished & (nxt != eos)
             ids = torch.cat((ids, nxt), dim=1)
-            if eos is not None and eos >= 0 and not bool(unfinished.any()):
+            if use_eos and not bool(unfinished.any()):
                 break
             if stopping_criteria is not None and any(bool(c(ids, scores)) for c in stopping_criteria):
                 break
-        if cons is not None:
-            cons.check()
+        if chooser is not None:
+            chooser.finish()
         if return_logprobs:
             return ids, (torch.stack(lps, dim=1) if lps else torch.empty((ids.shape[0], 0), dtype=torch.float32, device=ids.device))
         return ids
-
-    def _generate_ragged(self, input_ids, attention_mask, audio_encodings, max_new_tokens, do_sample, stopping_criteria, eos_token_id,
-                         temperature, sampling=None, return_logprobs=False, constraints=None):
-        """generate() over a padded batch: row b is the sequence input_ids[b][mask[b]] at positions 0 .. len_b - 1 (HF's
-        position_ids = cumsum(mask) - 1), one engine slot per row (prefill_slots / decode_slots).  Returns the HF layout: the input
-        as given followed by the new tokens; rows that finished emit the pad token."""
-        eng = self.engine
-        B, S = input_ids.shape
-        am = attention_mask.to(device="cpu", dtype=torch.bool)
-        if am.shape != (B, S):
-            raise ValueError(f"attention_mask shape {tuple(am.shape)} does not match input_ids {(B, S)}")
-        lens = am.sum(1)
-        if bool((lens == 0).any()):
-            raise ValueError("attention_mask selects no token in some row")
-        ids_dev = input_ids.to(eng.device)
-        if max_new_tokens <= 0:
-            return (ids_dev, torch.empty((B, 0), dtype=torch.float32, device=eng.device)) if return_logprobs else ids_dev
-        ids_cpu = input_ids.detach().cpu()
-        rows = [ids_cpu[b][am[b]] for b in range(B)]
-        packed = torch.zeros((B, int(lens.max())), dtype=torch.int64)               # right-aligned copy for the splice plan
-        for b, r in enumerate(rows):
-            packed[b, : r.numel()] = r
-        segs = []
-        if audio_encodings is not None:
-            feats = audio_encodings
-            if isinstance(feats, (list, tuple)):
-                feats = [f.to(device=eng.device, dtype=torch.float32) for f in feats]
-            else:
-                feats = feats.to(device=eng.device, dtype=torch.float32)
-            segs = plan_audio_splice(packed, feats, self.model.audio_encoder_config, False)
-        eos = eos_token_id if eos_token_id is not None else getattr(self.generation_config, "eos_token_id", None)
-        pad = getattr(self.generation_config, "pad_token_id", None)
-        pad = eos if pad is None else pad
-        use_eos = eos is not None and eos >= 0
-        eos_k, pad_k = (int(eos), int(pad)) if use_eos else (-1, 0)
-
-        def sample(scores):
-            return torch.multinomial(torch.softmax(scores / max(temperature, 1e-6), dim=-1), 1).view(-1)
-
-        out = torch.empty((B, S + max_new_tokens), dtype=torch.int64, device=eng.device)
-        out[:, :S] = ids_dev
-        eng.init_slots(B)
-        scores = eng.prefill_slots([r.to(eng.device) for r in rows], segs, range(B))
-        if sampling is not None:
-            sampler = DeviceSampler(sampling, B, scores.shape[-1], eng.device)
-            sampler.admit(range(B), rows, range(B))
-            do_sample = True                                                        # the callable below decides, penalised greedy included
-
-            def sample(scores):
-                return sampler(scores, state=eng.slot_state)
-        cons = None
-        if constraints is not None:                                                 # the choice, whichever it is, reads the processed rows
-            cons = DeviceConstraints(constraints, B, scores.shape[-1], int(lens.max()) + max_new_tokens, eng.device, eos_k)
-            cons.admit(range(B), rows)
-            constrained = cons.wrap(sample if do_sample else None)
-            do_sample = True
-
-            def sample(scores):
-                return constrained(scores, state=eng.slot_state)
-        tracker = None
-        if return_logprobs:
-            tracker, pick = ragged_logprob_hook(eng, B, scores.shape[-1], max_new_tokens, sample if do_sample else None)
-            sample, do_sample = pick, True
-        nxt, _ = eng.advance_slots(scores, eos_k, pad_k, out[:, S], sample(scores) if do_sample else None, advance=False)
-        n = 1
-        while True:
-            cur = out[:, : S + n]
-            if use_eos and all(st != ops.ROW_ACTIVE for st in eng.slot_state_host):
-                break
-            if stopping_criteria is not None and any(bool(c(cur, scores)) for c in stopping_criteria):
-                break
-            if n == max_new_tokens:
-                break
-            nxt, _, scores = eng.decode_slots(nxt, eos_k, pad_k, out[:, S + n], sample if do_sample else None)
-            n += 1
-        if cons is not None:
-            cons.check()
-        if tracker is not None:
-            return out[:, : S + n], ragged_logprob_matrix(tracker, n)
-        return out[:, : S + n]
 
     def _generate_beam(self, input_ids, attention_mask, audio_encodings, max_new_tokens, stopping_criteria, eos_token_id, num_beams,
                        length_penalty, early_stopping, num_return_sequences, return_logprobs, share_prefix, constraints=None):
@@ -577,27 +485,10 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
         eng = self.engine
         N, S = input_ids.shape
         B, R, lp = check_beam_args(num_beams, num_return_sequences, length_penalty, N)
-        am = torch.ones((N, S), dtype=torch.bool) if attention_mask is None else attention_mask.to(device="cpu", dtype=torch.bool)
-        if am.shape != (N, S):
-            raise ValueError(f"attention_mask shape {tuple(am.shape)} does not match input_ids {(N, S)}")
-        lens = am.sum(1)
-        if bool((lens == 0).any()):
-            raise ValueError("attention_mask selects no token in some row")
+        rows, lens, packed = unpack_prompts(input_ids, attention_mask)
         if max_new_tokens <= 0:
             raise ValueError(f"beam search needs max_new_tokens >= 1, got {max_new_tokens}")
-        ids_cpu = input_ids.detach().cpu()
-        rows = [ids_cpu[b][am[b]] for b in range(N)]
-        packed = torch.zeros((N, int(lens.max())), dtype=torch.int64)
-        for b, r in enumerate(rows):
-            packed[b, : r.numel()] = r
-        segs = []
-        if audio_encodings is not None:
-            feats = audio_encodings
-            if isinstance(feats, (list, tuple)):
-                feats = [f.to(device=eng.device, dtype=torch.float32) for f in feats]
-            else:
-                feats = feats.to(device=eng.device, dtype=torch.float32)
-            segs = plan_audio_splice(packed, feats, self.model.audio_encoder_config, False)
+        segs = plan_splice_on(eng.device, packed, audio_encodings, self.model.audio_encoder_config)
         eos = eos_token_id if eos_token_id is not None else getattr(self.generation_config, "eos_token_id", None)
         pad = getattr(self.generation_config, "pad_token_id", None)
         pad = eos if pad is None else pad
@@ -608,9 +499,9 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
         use_eos = eos is not None and eos >= 0
         pad_k = int(pad) if use_eos and pad is not None and pad >= 0 else 0       # the pad token is fed to the embedding: a valid id
         beam = BeamSearch(N, B, scores.shape[-1], max_new_tokens, eng.device, eos if use_eos else None, pad_k, lp, early_stopping)
-        beam.admit([int(n) for n in lens])
+        beam.admit(lens)
         if constraints is not None:                                                # every beam of an example starts from its prompt
-            beam.constraints = DeviceConstraints(constraints, N * B, scores.shape[-1], int(lens.max()) + max_new_tokens, eng.device,
+            beam.constraints = DeviceConstraints(constraints, N * B, scores.shape[-1], max(lens) + max_new_tokens, eng.device,
                                                  eos if use_eos else None)
             beam.constraints.admit(range(N * B), [rows[s // B] for s in range(N * B)])
         if getattr(self, "beam_observer", None) is not None:                       # tests: install the BeamSearch hooks before the first step

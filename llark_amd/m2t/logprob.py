@@ -58,27 +58,3 @@ class LogprobTracker:
             return []
         packed = torch.cat((self.hist[idx], self.count[idx].to(torch.float32)[:, None]), dim=1).cpu()      # counts <= 2^24: exact in fp32
         return [packed[i, : min(int(packed[i, -1]), self.width)].clone() for i in range(len(idx))]
-
-
-def ragged_logprob_hook(eng, n_slots: int, vocab: int, width: int, sample=None):
-    """For a wrapper's padded ``generate``: ``(tracker, pick)`` where ``pick(scores) -> tokens`` chooses the step's tokens -- by
-    ``sample`` (a callable scores -> tokens), else by the advance kernel's own first-maximum rule (``ops.sample_rows`` with
-    ``do_sample=False``) -- and then records, in one more launch on the same scores, their log-probabilities under the raw logits for
-    the slots that are still active."""
-    tracker = LogprobTracker(n_slots, vocab, eng.device, width)
-
-    def pick(scores):
-        if sample is not None:
-            tokens = sample(scores)
-        else:
-            tokens = ops.sample_rows(scores, torch.zeros((scores.shape[0],), dtype=torch.int64, device=scores.device),
-                                     state=eng.slot_state, do_sample=False, repetition_penalty=1.0)
-        tracker(scores, tokens, state=eng.slot_state)
-        return tokens
-    return tracker, pick
-
-
-def ragged_logprob_matrix(tracker: LogprobTracker, n: int) -> torch.Tensor:
-    """fp32 [n_slots, n] on the device: each slot's history, NaN from its ``count`` on (where a finished row emitted padding)."""
-    cols = torch.arange(n, device=tracker.device)[None, :]
-    return torch.where(cols < tracker.count[:, None], tracker.hist[:, :n], torch.full((), float("nan"), device=tracker.device))

@@ -26,11 +26,11 @@ from transformers.modeling_outputs import CausalLMOutputWithPast
 
 from .. import ops
 from . import AudioEncoderConfig
-from .llamav2 import EngineCache, plan_audio_splice
-from .logprob import ragged_logprob_hook, ragged_logprob_matrix
+from .choice import TokenChooser, generate_padded, unpack_prompts
+from .llamav2 import EngineCache, plan_splice_on
 from .mpt_engine import HipMptEngine, MptDims
-from .constraints import DeviceConstraints, constraints_from_generate
-from .sampling import DeviceSampler, params_from_generate
+from .constraints import constraints_from_generate
+from .sampling import params_from_generate
 from .special_tokens import DEFAULT_AUDIO_END_TOKEN, DEFAULT_AUDIO_PATCH_TOKEN, DEFAULT_AUDIO_START_TOKEN
 
 ATTN_DEFAULTS = dict(attn_type="multihead_attention", attn_pdrop=0.0, attn_impl="torch", qk_ln=False, clip_qkv=None, softmax_scale=None,
@@ -271,9 +271,7 @@ class WrappedMPTForCausalLM(nn.Module):
         cached = isinstance(past_key_values, EngineCache) and len(past_key_values) > 0
         segs = []
         if audio_encodings is not None and self.config.use_mm_proj and not cached:
-            feats = audio_encodings
-            feats = [f.to(eng.device, torch.float32) for f in feats] if isinstance(feats, (list, tuple)) else feats.to(eng.device, torch.float32)
-            segs = plan_audio_splice(ids, feats, self.transformer.audio_encoder_config, False, patch_branch=True)
+            segs = plan_splice_on(eng.device, ids, audio_encodings, self.transformer.audio_encoder_config, patch_branch=True)
         logits = eng.forward_tokens(ids, segs, pos0=eng.cur_len if cached else 0)
         loss = None
         if labels is not None:
@@ -302,7 +300,7 @@ class WrappedMPTForCausalLM(nn.Module):
                  bad_words_ids=None, suppress_tokens=None, min_new_tokens: Optional[int] = None, min_length: Optional[int] = None, **kwargs):
         """Generation loop driven by :meth:`prepare_inputs_for_generation` (prompt with audio once, then one token per step).  An
         ``attention_mask`` with zeros (left- or right-padded) runs every row as if it were alone on the engine's ragged slot mode
-        (:meth:`_generate_ragged`); ``None`` or all ones takes this uniform path and never enters the slot mode.
+        (:func:`llark_amd.m2t.choice.generate_padded`); ``None`` or all ones takes this uniform path and never enters the slot mode.
 
         Greedy by default.  ``do_sample`` (with ``temperature``, ``top_k``, ``top_p``, ``repetition_penalty``, ``seed``; ``top_k`` None or
         0: off) chooses every token with the device sampler (:mod:`llark_amd.m2t.sampling`, HF 4.29.2's processor order; Philox draws
@@ -323,33 +321,32 @@ class WrappedMPTForCausalLM(nn.Module):
             raise NotImplementedError(f"num_beams={num_beams!r}: beam search is not implemented for MPT (no K/V fork path there yet)")
         constraints = constraints_from_generate(no_repeat_ngram_size, bad_words_ids, suppress_tokens, min_new_tokens, min_length)
         sampling = params_from_generate(do_sample, temperature, top_k, top_p, repetition_penalty, seed, always=bool(do_sample))
+        eng = self.engine
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
-            return self._generate_ragged(input_ids, attention_mask, audio_encodings, max_new_tokens, stopping_criteria, eos_token_id,
-                                         pad_token_id, sampling, return_logprobs, constraints)
-        ids = input_ids.to(self.engine.device)
+            rows, _, packed = unpack_prompts(input_ids, attention_mask)
+            segs = []
+            if self.config.use_mm_proj:
+                segs = plan_splice_on(eng.device, packed, audio_encodings, self.transformer.audio_encoder_config, patch_branch=True)
+            use_eos = eos_token_id is not None and eos_token_id >= 0
+            eos_k, pad_k = (int(eos_token_id), int(eos_token_id if pad_token_id is None else pad_token_id)) if use_eos else (-1, 0)
+            return generate_padded(eng, rows, segs, input_ids, eos_k, pad_k, max_new_tokens, stopping_criteria, sampling=sampling,
+                                   constraints=constraints, return_logprobs=return_logprobs)
+        ids = input_ids.to(eng.device)
+
+        def choose(rows):
+            return rows.argmax(-1, keepdim=True)
+        chooser = TokenChooser.build(ids.shape[0], eng.dims.vocab_size, ids.device, sampling=sampling, constraints=constraints,
+                                     history_len=ids.shape[1] + max_new_tokens, eos=eos_token_id, choose=choose)
+        if chooser is not None:
+            chooser.admit(range(ids.shape[0]), list(input_ids))
         past = None
-        sampler = cons = None
         lps = []
         for _ in range(max_new_tokens):
             inp = self.prepare_inputs_for_generation(ids, past_key_values=past, audio_encodings=audio_encodings)
             out = self.forward(inp["input_ids"], past_key_values=inp["past_key_values"], audio_encodings=inp["audio_encodings"])
             past = out.past_key_values
             scores = out.logits[:, -1]
-            chosen_from = scores                                                              # the row the token is chosen from
-            if constraints is not None:
-                if cons is None:
-                    cons = DeviceConstraints(constraints, ids.shape[0], scores.shape[-1], ids.shape[1] + max_new_tokens, ids.device, eos_token_id)
-                    cons.admit(range(ids.shape[0]), list(input_ids))
-                    chosen_from = cons.process(scores)
-                else:
-                    chosen_from = cons.process(scores, last=ids[:, -1])
-            if sampling is not None:
-                if sampler is None:
-                    sampler = DeviceSampler(sampling, ids.shape[0], scores.shape[-1], ids.device)
-                    sampler.admit(range(ids.shape[0]), list(ids), range(ids.shape[0]))
-                nxt = sampler(chosen_from).view(-1, 1)
-            else:
-                nxt = chosen_from.argmax(-1, keepdim=True)
+            nxt = (choose if chooser is None else chooser)(scores).view(-1, 1)
             if return_logprobs:
                 lps.append(ops.token_logprob_rows(scores, nxt.view(-1).contiguous(),
                                                   torch.full((ids.shape[0],), float("nan"), dtype=torch.float32, device=ids.device)))
@@ -358,75 +355,8 @@ class WrappedMPTForCausalLM(nn.Module):
                 break
             if stopping_criteria is not None and any(bool(c(ids, scores)) for c in stopping_criteria):
                 break
-        if cons is not None:
-            cons.check()
+        if chooser is not None:
+            chooser.finish()
         if return_logprobs:
             return ids, (torch.stack(lps, dim=1) if lps else torch.empty((ids.shape[0], 0), dtype=torch.float32, device=ids.device))
         return ids
-
-    def _generate_ragged(self, input_ids, attention_mask, audio_encodings, max_new_tokens, stopping_criteria, eos_token_id, pad_token_id,
-                         sampling=None, return_logprobs=False, constraints=None):
-        """generate() over a padded batch (``WrappedLlamav2ForCausalLM._generate_ragged``): row b is the sequence
-        input_ids[b][mask[b]] at positions 0 .. len_b - 1, one engine slot per row (prefill_slots / decode_slots).  Returns the HF
-        layout: the input as given followed by the new tokens; a row that emitted EOS continues with the pad token (EOS when none)."""
-        eng = self.engine
-        B, S = input_ids.shape
-        am = attention_mask.to(device="cpu", dtype=torch.bool)
-        if am.shape != (B, S):
-            raise ValueError(f"attention_mask shape {tuple(am.shape)} does not match input_ids {(B, S)}")
-        lens = am.sum(1)
-        if bool((lens == 0).any()):
-            raise ValueError("attention_mask selects no token in some row")
-        ids_dev = input_ids.to(eng.device)
-        if max_new_tokens <= 0:
-            return (ids_dev, torch.empty((B, 0), dtype=torch.float32, device=eng.device)) if return_logprobs else ids_dev
-        ids_cpu = input_ids.detach().cpu()
-        rows = [ids_cpu[b][am[b]] for b in range(B)]
-        packed = torch.zeros((B, int(lens.max())), dtype=torch.int64)               # left-aligned copy for the splice plan
-        for b, r in enumerate(rows):
-            packed[b, : r.numel()] = r
-        segs = []
-        if audio_encodings is not None and self.config.use_mm_proj:
-            feats = audio_encodings
-            feats = [f.to(eng.device, torch.float32) for f in feats] if isinstance(feats, (list, tuple)) else feats.to(eng.device, torch.float32)
-            segs = plan_audio_splice(packed, feats, self.transformer.audio_encoder_config, False, patch_branch=True)
-        use_eos = eos_token_id is not None and eos_token_id >= 0
-        eos_k, pad_k = (int(eos_token_id), int(eos_token_id if pad_token_id is None else pad_token_id)) if use_eos else (-1, 0)
-        out = torch.empty((B, S + max_new_tokens), dtype=torch.int64, device=eng.device)
-        out[:, :S] = ids_dev
-        eng.init_slots(B)
-        scores = eng.prefill_slots([r.to(eng.device) for r in rows], segs, range(B))
-        sample = None
-        if sampling is not None:
-            sampler = DeviceSampler(sampling, B, scores.shape[-1], eng.device)
-            sampler.admit(range(B), rows, range(B))
-
-            def sample(scores):
-                return sampler(scores, state=eng.slot_state)
-        cons = None
-        if constraints is not None:                                                 # the choice, whichever it is, reads the processed rows
-            cons = DeviceConstraints(constraints, B, scores.shape[-1], int(lens.max()) + max_new_tokens, eng.device, eos_k)
-            cons.admit(range(B), rows)
-            constrained = cons.wrap(sample)
-
-            def sample(scores):
-                return constrained(scores, state=eng.slot_state)
-        tracker = None
-        if return_logprobs:
-            tracker, sample = ragged_logprob_hook(eng, B, scores.shape[-1], max_new_tokens, sample)
-        nxt, _ = eng.advance_slots(scores, eos_k, pad_k, out[:, S], None if sample is None else sample(scores), advance=False)
-        n = 1
-        while True:
-            if use_eos and all(st != ops.ROW_ACTIVE for st in eng.slot_state_host):
-                break
-            if stopping_criteria is not None and any(bool(c(out[:, : S + n], scores)) for c in stopping_criteria):
-                break
-            if n == max_new_tokens:
-                break
-            nxt, _, scores = eng.decode_slots(nxt, eos_k, pad_k, out[:, S + n], sample)
-            n += 1
-        if cons is not None:
-            cons.check()
-        if tracker is not None:
-            return out[:, : S + n], ragged_logprob_matrix(tracker, n)
-        return out[:, : S + n]

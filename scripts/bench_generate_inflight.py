@@ -66,11 +66,10 @@ class _NoText:
 
 
 class RandomLlama:
-    """The generate surface of WrappedLlamav2ForCausalLM (its own generate / ragged generate code) over a HipLlamaEngine with random
+    """The generate surface of WrappedLlamav2ForCausalLM (its own generate code, padded batches included) over a HipLlamaEngine with random
     Llama-2-7B weights: building the HF module at 7B on the host would take minutes and ~27 GB for weights that are random anyway."""
 
     generate = WrappedLlamav2ForCausalLM.generate
-    _generate_ragged = WrappedLlamav2ForCausalLM._generate_ragged
     prepare_inputs_for_generation = WrappedLlamav2ForCausalLM.prepare_inputs_for_generation
 
     def __init__(self, precision: str, max_batch: int, max_seq: int):
@@ -375,7 +374,8 @@ def main_logprobs(args, slot_list):
 def main_constraints(args, slot_list):
     import statistics
 
-    from llark_amd.m2t.constraints import DeviceConstraints, TokenConstraints
+    from llark_amd.m2t.choice import TokenChooser
+    from llark_amd.m2t.constraints import TokenConstraints
     steps, blocks = 16, 8
     examples = make_examples(64, args.seed)
     max_seq = max(ids.numel() for ids, _, _ in examples) + 8 + steps * (2 * blocks + 2)
@@ -388,16 +388,14 @@ def main_constraints(args, slot_list):
         eng.init_slots(n)
         rows = [examples[i % len(examples)] for i in range(n)]
         logits = eng.prefill_slots([r[0].cuda() for r in rows], [(k, 1, r[1].cuda()) for k, r in enumerate(rows)], range(n))
-        cons = DeviceConstraints(tc, n, logits.shape[-1], eng.smax + 1, eng.device, eos=2)
-        cons.admit(range(n), [r[0] for r in rows])
-        constrained = cons.wrap(None)                            # greedy on the processed rows: one constrain_rows + one sample_rows launch
-        kinds = {"greedy": None, "constrained": lambda lg: constrained(lg, state=eng.slot_state)}
-        ids = constrained(logits, state=eng.slot_state)
+        chooser = TokenChooser(n, logits.shape[-1], eng.device, constraints=tc, history_len=eng.smax + 1, eos=2)
+        chooser.admit(range(n), [r[0] for r in rows])            # greedy on the processed rows: one constrain_rows + one sample_rows launch
+        cons = chooser.cons
+        kinds = {"greedy": None, "constrained": lambda lg: chooser(lg, state=eng.slot_state)}
+        ids = chooser(logits, state=eng.slot_state)
 
-        def block(kind):
+        def block(kind):                                         # a history holds the constrained blocks' tokens only: the timing is the point
             nonlocal ids
-            if kind == "constrained":
-                cons.remember(ids)                               # the tokens the last step, of either kind, handed out
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(steps):
