@@ -663,6 +663,15 @@ int llark_beam_advance(const float* cand_score, const int* cand_token, const flo
 int llark_kv_copy_slots(void* k_cache, void* vt_cache, void* k_cache_lo, void* vt_cache_lo, int layers, int slots, int nh, int hd, int smax,
                         const int* pairs, const int* count, int n_lists, int list_stride, const int* p0, const int* pos_rows, int max_span,
                         llark_stream_t stream);
+/* llark_beam_advance_open: llark_beam_advance for a search inside a closed set (llark_guide_rows), where an example soon has fewer
+ * continuations than beams.  Two differences: a candidate whose cand_score is -inf is never taken (the row of a slot that holds no
+ * beam: its score is -inf, as the left-over slots of llark_beam_advance are written), and an example with fewer than B live beams goes
+ * on -- done[e] is set when NO live beam was found, or by the heap rule.  The left-over slots stay LLARK_ROW_ACTIVE, are fed pad, and
+ * take a beam again when a later step forks into them (their K/V span is copied whole, from p0).  Everything else as llark_beam_advance. */
+int llark_beam_advance_open(const float* cand_score, const int* cand_token, const float* cand_logprob, int n_examples, int beams, int step,
+                            int max_steps, int64_t eos, int64_t pad, float length_penalty, int early_stopping, float* score,
+                            int* rank_of_slot, int* state, int* pos_rows, int* cur_len, int64_t* next_ids, int* heap, int* heap_meta,
+                            int* done, int* trellis, int* pairs, int* pair_count, llark_stream_t stream);
 /* Constrained decoding on the device (csrc/constrain.hip): the tokens that HF 4.29.2's NoRepeatNGram, NoBadWords, MinLength and
  * MinNewTokensLength processors ban for a row's next choice, from the row's token history, which lives in device memory.
  *   llark_constrain_rows: one workgroup of 1024 threads per row r of logits fp32 [rows][ldl]; slot_of_row, state and the skip rules are
@@ -705,6 +714,40 @@ int llark_constrain_rows(const float* logits, int ldl, int vocab, int rows, int 
 int llark_beam_topk_rows_banned(const float* logits, int ldl, int vocab, int rows, int slots, const int* state, const int* slot_of_row,
                                 const float* score, int beams, float* cand_score, int* cand_token, float* cand_logprob, int* fallbacks,
                                 const unsigned* ban, int ld_ban, llark_stream_t stream);
+/* Guided choice on the device (csrc/guide.hip): a row may only continue inside a closed set of token sequences -- HF 4.29.2's
+ * PrefixConstrainedLogitsProcessor with the set given as data, a prefix tree in device memory, instead of a host callback.
+ *   llark_guide_rows: one workgroup of 1024 threads per row r of logits fp32 [rows][ldl]; slot_of_row, state and the skip rules are those
+ *     of llark_token_logprob_rows (a skipped row: nothing read, nothing written, its node untouched in BOTH buffers).
+ *     Table (CSR, read only): child_off int32 [n_nodes + 1]; child_tok int32 [n_edges], ascending and distinct within a node; child_node
+ *       int32 [n_edges]; terminal int32 [n_nodes] (non-zero: a whole sequence ends here).  The roots of all sets of a call are nodes of
+ *       the one table.  Per-slot state: node_in int32 [slots] is only read, node_out int32 [slots] only written (two buffers; the caller
+ *       swaps them after the launch): under beams a slot reads its parent's node while the parent's own workgroup advances it.  Node
+ *       values: >= 0 a node of the table, -1 unconstrained, -2 closed (only eos is allowed); anything else counts as -2.
+ *     In order:
+ *       1. parent (nullable) is int32 with an element stride, as in llark_constrain_rows -- a trellis column can be passed as it lies.
+ *          p = parent[slot * parent_stride]; p outside [0, slots) counts as p = slot.  n = node_in[p].
+ *       2. advance: last_token int64 [slots] (nullable: a prefill row) holds the token this row's logits were computed from.  When it
+ *          is given and n >= 0: n' = the child of n under that token; without such a child n' = -2, and bit 1 of *status (nullable) is
+ *          set unless the token is eos and terminal[n] is set.  With n < 0 or a prefill row n' = n.  Then node_out[slot] = n'.
+ *       3. allowed: the tokens of the children of n'; eos when terminal[n'] is set or n' == -2; everything when n' == -1.  A child token
+ *          outside [0, vocab) allows nothing.  A fan-out above 1024 is strided over the threads.
+ *       4. outputs, each nullable but not all three: out fp32 [rows][ldo] = the row's raw bits (NaN and -inf included) at allowed
+ *          columns, -inf elsewhere; out == logits with ldo == ldl is in place; columns >= vocab are not written.  ban uint32
+ *          [slots][ld_ban], row of the SLOT, in the layout of llark_constrain_rows (bit set: NOT allowed; bits of columns >= vocab stay
+ *          clear): stored, or with ban_accumulate != 0 OR-ed into what is there, so that it composes with that kernel's bitmap for
+ *          llark_beam_topk_rows_banned.  n_open int32 [rows]: the allowed columns whose logit is neither -inf nor NaN; when it is 0,
+ *          bit 2 of *status is set.
+ *     Caps: vocab <= 65536 (LLARK_ERR_UNSUPPORTED above, as llark_sample_rows), n_nodes in 1 .. 2^20, n_edges <= 2^20.
+ *     LLARK_ERR_INVALID before any launch: a null logits / child_off / terminal / node_in / node_out, edges without child_tok /
+ *     child_node, all of out / ban / n_open null, rows, slots or vocab <= 0, ldl < vocab, rows > slots without slot_of_row, a table
+ *     above the caps, node_in == node_out, parent_stride < 1, eos outside [0, vocab), ldo < vocab (in place: ldo != ldl), ld_ban <
+ *     ceil(vocab / 32).
+ *     No workgroup waits for another; the allowed set is built in LDS; the only global atomic is the OR on *status. */
+int llark_guide_rows(const float* logits, int ldl, int vocab, int rows, int slots, const int* state, const int* slot_of_row,
+                     const int* child_off, const int* child_tok, const int* child_node, const int* terminal, int n_nodes, int n_edges,
+                     const int* node_in, int* node_out, const int* parent, int parent_stride, const int64_t* last_token, int64_t eos,
+                     float* out, int ldo, unsigned* ban, int ld_ban, int ban_accumulate, int* n_open, int* status,
+                     llark_stream_t stream);
 /* MPT ragged decode step, the whole attention front in one launch (m2t/llava/model/mpt/attention.py: qkv.clamp_ -> q_ln / k_ln ->
  * head split -> attention with the ALiBi bias; replaces llark_clamp_f32 + 2 x llark_layernorm_f32 + llark_attn_decode_rope_bf16_rows
  * with identity tables).  qkv fp32 [batch][ldq], laid out q | k | v with nh*128 columns each, is READ ONLY.  Workgroup (h, b) reads

@@ -185,6 +185,7 @@ struct BeamAdvanceArgs {
     long long eos, pad;
     float length_penalty;
     int early_stopping;
+    int open;                                                     // llark_beam_advance_open: an example goes on with fewer than B live beams
     float* score;
     int* rank_of_slot;
     int* state;
@@ -273,6 +274,7 @@ __global__ __launch_bounds__(64) void beam_advance_kernel(const BeamAdvanceArgs 
         const int t = ct[rk][h];
         if (k == 0) best0 = c;
         if (t < 0) continue;                                      // a row without a distribution: never taken
+        if (a.open && c == -INFINITY) continue;                   // open: the row of a slot that holds no beam
         if (a.eos >= 0 && t == a.eos) {
             if (k < B) beam_heap_add(heap, meta, B, c, cur_len, a.length_penalty, a.step, base + slot_of_rank[rk], lp);
             continue;
@@ -281,7 +283,7 @@ __global__ __launch_bounds__(64) void beam_advance_kernel(const BeamAdvanceArgs 
         if (first_child[slot_of_rank[rk]] < 0) first_child[slot_of_rank[rk]] = live;
         ++live;
     }
-    bool done = live < B;                                         // rows without candidates: the example cannot go on
+    bool done = a.open ? live == 0 : live < B;                    // rows without candidates: the example cannot go on
     if (!done && meta[0] >= B) {
         const float cur = (float)((double)best0 / pow((double)cur_len, (double)a.length_penalty));
         done = a.early_stopping || __int_as_float(meta[1]) >= cur;
@@ -392,10 +394,10 @@ extern "C" int llark_beam_topk_rows_banned(const float* logits, int ldl, int voc
     return check_launch("beam_topk_rows_banned");
 }
 
-extern "C" int llark_beam_advance(const float* cand_score, const int* cand_token, const float* cand_logprob, int n_examples, int beams,
-                                  int step, int max_steps, int64_t eos, int64_t pad, float length_penalty, int early_stopping, float* score,
-                                  int* rank_of_slot, int* state, int* pos_rows, int* cur_len, int64_t* next_ids, int* heap, int* heap_meta,
-                                  int* done, int* trellis, int* pairs, int* pair_count, llark_stream_t stream) {
+static int beam_advance_launch(int open, const float* cand_score, const int* cand_token, const float* cand_logprob, int n_examples, int beams,
+                               int step, int max_steps, int64_t eos, int64_t pad, float length_penalty, int early_stopping, float* score,
+                               int* rank_of_slot, int* state, int* pos_rows, int* cur_len, int64_t* next_ids, int* heap, int* heap_meta,
+                               int* done, int* trellis, int* pairs, int* pair_count, llark_stream_t stream) {
     LLARK_REQUIRE(cand_score && cand_token && cand_logprob && score && rank_of_slot && state && cur_len && next_ids && heap && heap_meta &&
                       done && trellis && pairs && pair_count,
                   "beam_advance: null pointer (only pos_rows may be null)");
@@ -408,9 +410,27 @@ extern "C" int llark_beam_advance(const float* cand_score, const int* cand_token
     a.eos = (long long)eos, a.pad = (long long)pad, a.length_penalty = length_penalty, a.early_stopping = early_stopping != 0;
     a.score = score, a.rank_of_slot = rank_of_slot, a.state = state, a.pos_rows = pos_rows, a.cur_len = cur_len;
     a.next_ids = (long long*)next_ids, a.heap = heap, a.heap_meta = heap_meta, a.done = done, a.trellis = trellis, a.pairs = pairs;
-    a.pair_count = pair_count;
+    a.pair_count = pair_count, a.open = open;
     beam_advance_kernel<<<n_examples, 64, 0, (hipStream_t)stream>>>(a);
     return check_launch("beam_advance");
+}
+
+extern "C" int llark_beam_advance(const float* cand_score, const int* cand_token, const float* cand_logprob, int n_examples, int beams,
+                                  int step, int max_steps, int64_t eos, int64_t pad, float length_penalty, int early_stopping, float* score,
+                                  int* rank_of_slot, int* state, int* pos_rows, int* cur_len, int64_t* next_ids, int* heap, int* heap_meta,
+                                  int* done, int* trellis, int* pairs, int* pair_count, llark_stream_t stream) {
+    return beam_advance_launch(0, cand_score, cand_token, cand_logprob, n_examples, beams, step, max_steps, eos, pad, length_penalty,
+                               early_stopping, score, rank_of_slot, state, pos_rows, cur_len, next_ids, heap, heap_meta, done, trellis, pairs,
+                               pair_count, stream);
+}
+
+extern "C" int llark_beam_advance_open(const float* cand_score, const int* cand_token, const float* cand_logprob, int n_examples, int beams,
+                                       int step, int max_steps, int64_t eos, int64_t pad, float length_penalty, int early_stopping,
+                                       float* score, int* rank_of_slot, int* state, int* pos_rows, int* cur_len, int64_t* next_ids, int* heap,
+                                       int* heap_meta, int* done, int* trellis, int* pairs, int* pair_count, llark_stream_t stream) {
+    return beam_advance_launch(1, cand_score, cand_token, cand_logprob, n_examples, beams, step, max_steps, eos, pad, length_penalty,
+                               early_stopping, score, rank_of_slot, state, pos_rows, cur_len, next_ids, heap, heap_meta, done, trellis, pairs,
+                               pair_count, stream);
 }
 
 extern "C" int llark_kv_copy_slots(void* k_cache, void* vt_cache, void* k_cache_lo, void* vt_cache_lo, int layers, int slots, int nh, int hd,

@@ -75,6 +75,11 @@ class BeamSearch:
         # a llark_amd.m2t.constraints.DeviceConstraints over the same slots (admitted by the caller): banned tokens are left out of the
         # candidates; None: the unconstrained launch
         self.constraints = None
+        # a llark_amd.m2t.guide.DeviceGuide over the same slots (admitted by the caller): tokens outside a slot's choice set are left
+        # out of the candidates too -- its bitmap is OR-ed into the constraints' when both are on; None: no such launch.  Inside a closed
+        # set an example soon has fewer continuations than beams: with a guide the step is ops.beam_advance(open=True), which goes on
+        # while ANY beam lives; a slot without a beam has the score -inf, is fed pad and is taken again when a later step forks into it
+        self.guide = None
 
     def admit(self, prompt_lens: Sequence[int]) -> None:
         """The examples' prompt lengths: cur_len, and the first position a K/V move has to copy (the slots of an example are clones of
@@ -101,16 +106,20 @@ class BeamSearch:
         if self.observe_logits is not None:
             self.observe_logits(self.steps, logits)
         ban = None
-        if self.constraints is not None:
+        if self.constraints is not None or self.guide is not None:
             if (last is None) != (self.steps == 0):
-                raise ValueError("BeamSearch.step: constraints need `last` on every step but the first")
-            ban = self.constraints.process(logits, state=state, last=last, parent=None if last is None else self.trellis[self.steps - 1, :, 0],
-                                           bitmap=True)
+                raise ValueError("BeamSearch.step: constraints and a guide need `last` on every step but the first")
+            parent = None if last is None else self.trellis[self.steps - 1, :, 0]
+            if self.constraints is not None:
+                ban = self.constraints.process(logits, state=state, last=last, parent=parent, bitmap=True)
+            if self.guide is not None:
+                ban = self.guide.process(logits, state=state, last=last, parent=parent, bitmap=True, ban=ban)
         ops.beam_topk_rows(logits, self.score, B, self.cand_score, self.cand_token, self.cand_logprob, vocab=self.vocab, state=state,
                            fallbacks=self.fallbacks, **({} if ban is None else dict(ban=ban)))
         ops.beam_advance(self.cand_score, self.cand_token, self.cand_logprob, N, B, self.steps, self.eos, self.pad, self.length_penalty,
                          self.early_stopping, self.score, self.rank_of_slot, state, pos_rows, self.cur_len, self.next_ids, self.heap,
-                         self.heap_meta, self.done, self.trellis, self.pairs, self.pair_count)
+                         self.heap_meta, self.done, self.trellis, self.pairs, self.pair_count,
+                         **({} if self.guide is None else dict(open=True)))
         for e in range(N):
             if not self.done_host[e]:
                 self.len_host[e] += 1
@@ -146,6 +155,8 @@ class BeamSearch:
             if not done[e]:
                 for r in range(B):
                     slot = e * B + int(np.nonzero(rank[e * B:e * B + B] == r)[0][0])
+                    if np.isneginf(score[slot]):                   # a slot without a beam (the open step)
+                        continue
                     sc = np.float32(np.float64(score[slot]) / np.float64(int(cur[e])) ** np.float64(self.length_penalty))
                     new = dict(score=sc, sum=score[slot], length=int(cur[e]), end_step=T, end_slot=slot, arrival=arrivals, eos_lp=float("nan"))
                     arrivals += 1

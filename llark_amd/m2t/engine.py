@@ -1032,7 +1032,7 @@ class HipLlamaEngine:
         B = beam.beams
         was_done = list(beam.done_host)
         kv = None if first else (self.k_cache, self.vt_cache, self.k_cache_lo, self.vt_cache_lo)
-        if getattr(beam, "constraints", None) is not None:
+        if getattr(beam, "constraints", None) is not None or getattr(beam, "guide", None) is not None:
             nxt, done = beam.step(logits, self.slot_state, None if first else self.slot_len, kv, last=ids)
         else:
             nxt, done = beam.step(logits, self.slot_state, None if first else self.slot_len, kv)

@@ -143,10 +143,14 @@ class InflightScheduler:
     repetition penalty, temperature, top-k or top-p is applied, for sampled tokens too -- and ``run`` yields ``(index, ids, logprobs)``
     with one entry per generated token, the EOS or keyword token included.  ``backend.take_logprobs(finished)`` (a list of 1-D
     tensors in the order of ``finished``) is called just before ``backend.release(finished)``.  Off (the default), the backend sees
-    no new call and ``run`` yields pairs."""
+    no new call and ``run`` yields pairs.
+
+    ``choices``: an example may carry a fifth element, the index of its choice set (None: unconstrained), and every ``prefill`` call
+    also gets ``choice=`` (the indices of its examples).  Off (the default), a fifth element is refused."""
 
     def __init__(self, backend, n_slots: int, max_new_tokens: int = 512, eos: Optional[int] = None, stop_fn=None,
-                 share_prefix: bool = False, min_shared: int = MIN_SHARED, sampling: bool = False, logprobs: bool = False):
+                 share_prefix: bool = False, min_shared: int = MIN_SHARED, sampling: bool = False, logprobs: bool = False,
+                 choices: bool = False):
         if n_slots < 1:
             raise ValueError(f"n_slots must be >= 1, got {n_slots}")
         self.backend, self.n_slots, self.max_new_tokens = backend, n_slots, max_new_tokens
@@ -154,12 +158,13 @@ class InflightScheduler:
         self.min_shared = min_shared
         self.sampling = bool(sampling)
         self.logprobs = bool(logprobs)
+        self.choices = bool(choices)
         self.eos = eos if eos is not None and eos >= 0 else None
         self.stop_fn = stop_fn                    # (prompt ids, generated ids) -> bool: keyword stop; may keep state per row
         self.trace: List[Tuple] = []
 
     def run(self, examples: Iterable[Sequence[Any]]) -> Iterator[Tuple[int, torch.Tensor]]:
-        """examples: (prompt_ids, encoding[, max_new_tokens[, prefix_key]]).  Yields (input index, prompt + generated ids) as rows finish; rows
+        """examples: (prompt_ids, encoding[, max_new_tokens[, prefix_key[, choice set index]]]).  Yields (input index, prompt + generated ids) as rows finish; rows
         finishing in the same step come out in input order.  With ``logprobs``: (input index, ids, log-probabilities of the generated
         tokens under the model's raw logits)."""
         it = enumerate(examples)
@@ -176,9 +181,11 @@ class InflightScheduler:
                     break
                 prompt = torch.as_tensor(ex[0], dtype=torch.int64).reshape(-1).cpu()
                 budget = int(ex[2]) if len(ex) > 2 and ex[2] is not None else self.max_new_tokens
+                if len(ex) > 4 and ex[4] is not None and not self.choices:
+                    raise ValueError(f"example {idx} names the choice set {ex[4]!r}, but no choice_sets were given")
                 b = free.pop(0)
                 table[b] = {"index": idx, "prompt": prompt, "enc": ex[1], "budget": budget, "out": [], "stop": None,
-                            "key": ex[3] if len(ex) > 3 else None}
+                            "key": ex[3] if len(ex) > 3 else None, "choice": ex[4] if len(ex) > 4 else None}
                 new.append(b)
             if new:
                 done = self._take(table, self._admit(table, new))
@@ -199,7 +206,10 @@ class InflightScheduler:
         toks: Dict[int, int] = {}
 
         def extra(slots):
-            return dict(indices=[table[b]["index"] for b in slots], whole=[table[b]["prompt"] for b in slots]) if self.sampling else {}
+            kw = dict(indices=[table[b]["index"] for b in slots], whole=[table[b]["prompt"] for b in slots]) if self.sampling else {}
+            if self.choices:
+                kw["choice"] = [table[b]["choice"] for b in slots]
+            return kw
         if full:
             self.trace.append(("prefill", tuple(full), tuple(table[b]["index"] for b in full)))
             toks.update(zip(full, self.backend.prefill(full, [table[b]["prompt"] for b in full], [table[b]["enc"] for b in full],
@@ -283,10 +293,13 @@ class EngineSlots:
     (:class:`llark_amd.m2t.logprob.LogprobTracker`, one launch per step); ``take_logprobs(slots)`` reads finished slots' histories.
     ``constraints`` (a :class:`llark_amd.m2t.constraints.TokenConstraints`): every choice, greedy or sampled, is made on the logits with
     -inf at the tokens its example's history bans (one more launch per step, no transfer); the EOS of ``min_new_tokens`` /
-    ``min_length`` is the model's ``generation_config.eos_token_id``.  The stages that are on run in the order of one
+    ``min_length`` is the model's ``generation_config.eos_token_id``.  ``choice_sets`` (a :class:`llark_amd.m2t.guide.ChoiceSets`):
+    an example that names one of the sets only continues inside it (one more launch per step, no transfer); the EOS a whole sequence
+    allows is the same ``eos_token_id``, which must exist.  The stages that are on run in the order of one
     :class:`llark_amd.m2t.choice.TokenChooser`."""
 
-    def __init__(self, model, n_slots: int, share_prefix: bool = False, sampling=None, logprobs: bool = False, constraints=None):
+    def __init__(self, model, n_slots: int, share_prefix: bool = False, sampling=None, logprobs: bool = False, constraints=None,
+                 choice_sets=None):
         from .llamav2 import plan_audio_splice
 
         self._plan = plan_audio_splice
@@ -301,8 +314,14 @@ class EngineSlots:
         self.ids = torch.zeros((n_slots,), dtype=torch.int64, device=self.eng.device)
         stages = dict(sampling=sampling if sampling is not None and sampling.active else None,
                       constraints=constraints if constraints is not None and constraints.active else None, logprobs=bool(logprobs))
+        if choice_sets is not None:
+            from .guide import require_eos
+
+            require_eos(getattr(getattr(model, "generation_config", None), "eos_token_id", None), "generation_config.eos_token_id")
+            stages["guide"] = choice_sets
         self.stages = stages if any(stages.values()) else None    # None: plain greedy calls, nothing launched or allocated
         self.chooser = None                                       # built at the first prefill, which tells the logits' width
+        self.index_of_slot = {}                                   # slot -> its example's input index (when the scheduler hands them on)
         cfg = model.get_model().audio_encoder_config
         self.audio_token_ids = tuple(int(t) for t in (getattr(cfg, name, None) for name in ("audio_start_token", "audio_end_token", "audio_patch_token"))
                                      if t is not None)
@@ -310,7 +329,7 @@ class EngineSlots:
     def fork(self, src, dsts, n):
         self.eng.fork_slots(src, dsts, n)
 
-    def prefill(self, slots, prompts, encodings, past=None, indices=None, whole=None):
+    def prefill(self, slots, prompts, encodings, past=None, indices=None, whole=None, choice=None):
         eng = self.eng
         cfg = self.model.get_model().audio_encoder_config
         segs = []
@@ -331,7 +350,9 @@ class EngineSlots:
                 # a history is at most the cache's smax positions plus the token just chosen: the engine refuses a slot beyond smax first
                 self.chooser = TokenChooser(self.n_slots, logits.shape[-1], eng.device, history_len=eng.smax + 1, logprob_width=eng.smax,
                                             eos=getattr(getattr(self.model, "generation_config", None), "eos_token_id", None), **self.stages)
-            self.chooser.admit(slots, prompts if whole is None else whole, indices)
+            self.chooser.admit(slots, prompts if whole is None else whole, indices, **({} if choice is None else dict(choice=choice)))
+            if indices is not None:
+                self.index_of_slot.update(zip(slots, indices))
             first = self.chooser(logits, state=eng.slot_state, slot_of_row=list(slots))
         self.ids[torch.tensor(slots, dtype=torch.long, device=eng.device)] = first
         return first.cpu().tolist()
@@ -349,17 +370,33 @@ class EngineSlots:
         return self.chooser.take_logprobs(slots)
 
     def release(self, slots):
+        self.check_guide(slots)
         self.eng.release_slots(slots)
         if self.chooser is not None:
             self.chooser.release(slots)
+
+    def check_guide(self, slots=()):
+        """Raises when a guided row had no allowed token left (every continuation inside its choice set was banned by the constraints)
+        or was handed a token outside its set: the guide's status word, read when examples are released -- before their completions
+        are handed out, so the example it happened to is never yielded -- and once more at the end of the run."""
+        if self.chooser is None or self.chooser.guide is None:
+            return
+        from .. import ops
+
+        try:
+            self.chooser.guide.check()
+        except RuntimeError as e:
+            now = [self.index_of_slot.get(b, f"slot {b}") for b in slots]
+            live = [i for b, i in sorted(self.index_of_slot.items()) if self.eng.slot_state_host[b] == ops.ROW_ACTIVE and b not in slots]
+            raise RuntimeError(f"generate_inflight: {e}; noticed at the release of example(s) {now}, examples still decoding: {live}") from e
 
 
 @torch.no_grad()
 def generate_inflight(model, examples: Iterable[Sequence[Any]], slots: int = 8, max_new_tokens: int = 512,
                       keywords: Sequence[str] = ("###",), tokenizer=None, trace: Optional[list] = None,
                       share_prefix: bool = False, sampling=None, return_logprobs: bool = False,
-                      num_beams: Optional[int] = None, constraints=None) -> Iterator[Tuple[int, torch.Tensor]]:
-    """Generation (greedy unless ``sampling``) with in-flight slot refill.  ``examples`` yields ``(prompt_ids, encoding[, max_new_tokens[, prefix_key]])`` with prompts
+                      num_beams: Optional[int] = None, constraints=None, choice_sets=None) -> Iterator[Tuple[int, torch.Tensor]]:
+    """Generation (greedy unless ``sampling``) with in-flight slot refill.  ``examples`` yields ``(prompt_ids, encoding[, max_new_tokens[, prefix_key[, choice]]])`` with prompts
     of any length; up to ``slots`` of them decode together, each at its own KV-cache length, and a finished row's slot is refilled
     from the iterable (contiguous free slots prefilled as one batch) while the others keep decoding.  Stops per row as in
     :func:`generate_batch` (keyword -- needs ``tokenizer`` --, EOS or budget).  Yields ``(index, prompt + continuation ids)`` as
@@ -377,7 +414,13 @@ def generate_inflight(model, examples: Iterable[Sequence[Any]], slots: int = 8, 
     :class:`llark_amd.m2t.constraints.TokenConstraints` (``no_repeat_ngram_size``, ``bad_words_ids``, ``suppress_tokens``,
     ``min_new_tokens``, ``min_length``), applied on the device to every choice from the example's own history -- its whole prompt under
     ``share_prefix`` too -- so a completion does not depend on ``slots``; an example's own ``max_new_tokens`` below ``min_new_tokens``
-    wins: the row stops at its budget.  Refused with a model's own ``slot_backend`` as sampling is."""
+    wins: the row stops at its budget.  Refused with a model's own ``slot_backend`` as sampling is.  ``choice_sets``: a list of choice
+    sets (each a non-empty list of non-empty token-id sequences; :mod:`llark_amd.m2t.guide`); an example's fifth element is the index
+    of its set, or None for an unconstrained example.  A guided example's new tokens are one of its set's sequences followed by the
+    model's ``generation_config.eos_token_id`` (required), whatever ``slots`` is -- unless a keyword or its budget stops it first.  When
+    ``constraints`` ban every continuation of a guided example the run raises a RuntimeError at the next release of examples, before
+    that example is yielded (``EngineSlots.check_guide``).
+    Refused with a model's own ``slot_backend`` as sampling is."""
     refuse_beams("generate_inflight", num_beams)
     if keywords and tokenizer is None:
         raise ValueError("generate_inflight: keyword stopping needs the tokenizer")
@@ -391,6 +434,12 @@ def generate_inflight(model, examples: Iterable[Sequence[Any]], slots: int = 8, 
     if constraints is not None and make is not None:
         raise ValueError("generate_inflight: constraints need the engine's own slot backend; this model provides slot_backend()")
     more = {} if constraints is None else dict(constraints=constraints)
+    if choice_sets is not None:
+        from .guide import ChoiceSets
+
+        if make is not None:
+            raise ValueError("generate_inflight: choice_sets need the engine's own slot backend; this model provides slot_backend()")
+        more["choice_sets"] = choice_sets if isinstance(choice_sets, ChoiceSets) else ChoiceSets(choice_sets)
     if make is not None:
         backend = make(slots)
     elif return_logprobs:
@@ -405,11 +454,13 @@ def generate_inflight(model, examples: Iterable[Sequence[Any]], slots: int = 8, 
                 row["stop"] = KeywordsStoppingCriteria(keywords=list(keywords), tokenizer=tokenizer, input_ids=row["prompt"][None])
             return bool(row["stop"](torch.cat((row["prompt"], gen))[None], None))
     sched = InflightScheduler(backend, slots, max_new_tokens, eos, stop_fn, share_prefix=share_prefix,
-                              sampling=sampling is not None or constraints is not None,
-                              **(dict(logprobs=True) if return_logprobs else {}))
+                              sampling=sampling is not None or constraints is not None or choice_sets is not None,
+                              **(dict(logprobs=True) if return_logprobs else {}), **(dict(choices=True) if choice_sets is not None else {}))
     if trace is not None:
         sched.trace = trace
     yield from sched.run(examples)
+    if choice_sets is not None:
+        backend.check_guide()
 
 
 @torch.no_grad()
@@ -592,7 +643,7 @@ def infer_from_shards(model, tokenizer, shards: str, multimodal_cfg: Dict[str, A
                       slots: int = 8, max_samples: Optional[int] = None, max_new_tokens: int = 512, prompt: Optional[str] = None,
                       seed: int = 0, allow_pickle: bool = False, header: str = DEFAULT_CONVERSATION_HEADER,
                       share_prefix: bool = False, sampling=None, logprobs: bool = False,
-                      num_beams: Optional[int] = None, constraints=None) -> List[Dict[str, str]]:
+                      num_beams: Optional[int] = None, constraints=None, choice_sets=None, choice_of=None) -> List[Dict[str, str]]:
     """Local tar shards -> CSV under the contract of ``scripts/inference/infer_from_webdataset.py:51-151``: every (question,
     answer) pair of a sample is one example whose prompt is its own human turn up to "### Assistant:" (audio placeholder first
     or last by a draw seeded with ``seed``); ``prompt`` overrides every question (the reference's ``--prompt``: audio first).
@@ -604,10 +655,20 @@ def infer_from_shards(model, tokenizer, shards: str, multimodal_cfg: Dict[str, A
     ``logprobs``: every record also gets ``sum_logprob``, ``mean_logprob`` and ``n_tokens`` over ALL generated tokens (the stop keyword or
     EOS included, although the completion text drops it): log-probabilities of the model's distribution -- log-softmax of the raw
     logits; repetition penalty, temperature, top-k and top-p are not applied, for sampled tokens too.  ``constraints``: a
-    :class:`llark_amd.m2t.constraints.TokenConstraints`, as in :func:`generate_inflight`."""
+    :class:`llark_amd.m2t.constraints.TokenConstraints`, as in :func:`generate_inflight`.  ``choice_sets``: the closed answer sets, as in
+    :func:`generate_inflight`; ``choice_of(conversation)`` -- the example's record, whose ``id`` is the sample's tar key -- returns the
+    index of its set or None for a free answer (default with ONE set: every example takes it)."""
     from .data import element_to_conversations, expand_urls, iter_tar_samples
 
     refuse_beams("infer_from_shards", num_beams)
+    if choice_of is not None and choice_sets is None:
+        raise ValueError("infer_from_shards: choice_of without choice_sets")
+    if choice_sets is not None and choice_of is None:
+        if len(choice_sets.sets if hasattr(choice_sets, "sets") else choice_sets) != 1:
+            raise ValueError("infer_from_shards: several choice_sets need choice_of, which names each example's set")
+
+        def choice_of(conv):
+            return 0
     rng = random.Random(seed)
     meta: List[Dict[str, str]] = []
 
@@ -626,13 +687,17 @@ def infer_from_shards(model, tokenizer, shards: str, multimodal_cfg: Dict[str, A
                     prompt_text = prompt
                 meta.append({"example_id": conv["id"], "prompt_text": prompt_text,
                              "original_completion_text": tokenizer.decode(extract_response_tokens(ex["input_ids"], end_seq))})
-                yield ids, enc, None, conv["id"]
+                if choice_sets is None:
+                    yield ids, enc, None, conv["id"]
+                else:
+                    yield ids, enc, None, conv["id"], choice_of(conv)
 
     outs: Dict[int, torch.Tensor] = {}
     lps: Dict[int, torch.Tensor] = {}
     for item in generate_inflight(model, examples(), slots=slots, max_new_tokens=max_new_tokens, tokenizer=tokenizer,
                                   share_prefix=share_prefix, sampling=sampling, **(dict(return_logprobs=True) if logprobs else {}),
-                                  **({} if constraints is None else dict(constraints=constraints))):
+                                  **({} if constraints is None else dict(constraints=constraints)),
+                                  **({} if choice_sets is None else dict(choice_sets=choice_sets))):
         outs[item[0]] = item[1]
         if logprobs:
             lps[item[0]] = item[2]
@@ -750,7 +815,7 @@ def main_shards(argv=None):
     python -m llark_amd.m2t.infer_driver shards --model_name_or_path <dir> --eval_data_path "shards-{000000..000021}.tar" \
         --outfile results/infer.csv [--prompt "Describe ..."] [--max-samples N] [--max_new_tokens 2048] [--slots 8] [--allow-pickle]
         [--share-prefix] [--do-sample --temperature 0.8 --top-k 50 --top-p 0.9 --sample-seed 0] [--repetition-penalty 1.3] [--logprobs]
-        [--no-repeat-ngram-size 3] [--min-new-tokens 8]
+        [--no-repeat-ngram-size 3] [--min-new-tokens 8] [--choices-json labels.json]
     ``--allow-pickle``: read ``.pyd`` (pickled) encodings -- unpickling runs code, pass it only for shards you trust."""
     import argparse
 
@@ -782,6 +847,8 @@ def main_shards(argv=None):
                     "(1 .. 64; 0: off); the bans are computed on the device from the example's own history")
     ap.add_argument("--min-new-tokens", type=int, default=0, help="the EOS token is banned for this many new tokens (0: off); an example's "
                     "own budget below it wins")
+    ap.add_argument("--choices-json", default=None, help="a file holding a JSON list of strings: the closed answer set of every example "
+                    "(each tokenised after a space, without special tokens); every completion is then one of them, chosen on the device")
     ap.add_argument("--mm_hidden_size", type=int, default=None)
     ap.add_argument("--model_max_length", type=int, default=2048)
     ap.add_argument("--llm-precision", default="split", choices=["split", "bf16"])
@@ -789,13 +856,18 @@ def main_shards(argv=None):
         ap.add_argument(ignored, default=None, help="accepted for script compatibility")
     args = ap.parse_args(argv)
     from .constraints import constraints_from_generate
+    from .guide import choices_from_json, choices_from_strings
     from .sampling import SamplingParams
 
     try:
+        choices = None
+        if args.choices_json is not None:
+            with open(args.choices_json) as f:
+                choices = choices_from_json(f.read())
         sampling = SamplingParams(do_sample=args.do_sample, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
                                   repetition_penalty=args.repetition_penalty, seed=args.sample_seed)
         constraints = constraints_from_generate(no_repeat_ngram_size=args.no_repeat_ngram_size, min_new_tokens=args.min_new_tokens)
-    except ValueError as e:
+    except (ValueError, OSError) as e:
         ap.error(str(e))
     if not 1 <= args.slots <= 64:
         ap.error(f"--slots must be in 1 .. 64, got {args.slots}")
@@ -809,7 +881,8 @@ def main_shards(argv=None):
                              max_samples=args.max_samples, max_new_tokens=args.max_new_tokens, prompt=args.prompt, seed=args.seed,
                              allow_pickle=args.allow_pickle, share_prefix=args.share_prefix, sampling=sampling if sampling.active else None,
                              **(dict(logprobs=True) if args.logprobs else {}),
-                             **({} if constraints is None else dict(constraints=constraints)))
+                             **({} if constraints is None else dict(constraints=constraints)),
+                             **({} if choices is None else dict(choice_sets=[choices_from_strings(tok, choices)])))
     print(f"writing {len(recs)} results to {args.outfile}")
     return recs
 

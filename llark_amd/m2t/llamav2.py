@@ -28,6 +28,7 @@ from . import AudioEncoderConfig
 from .beam import BeamSearch, check_beam_args
 from .choice import TokenChooser, generate_padded, unpack_prompts
 from .constraints import DeviceConstraints, constraints_from_generate
+from .guide import DeviceGuide, guide_from_generate, require_eos
 from .engine import HipLlamaEngine, LlamaDims
 from .sampling import params_from_generate
 from .special_tokens import DEFAULT_AUDIO_END_TOKEN, DEFAULT_AUDIO_PATCH_TOKEN, DEFAULT_AUDIO_START_TOKEN
@@ -382,7 +383,7 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
                  return_logprobs: bool = False, num_beams: Optional[int] = None, length_penalty: float = 1.0,
                  early_stopping: bool = False, num_return_sequences: Optional[int] = None, num_beam_groups: Optional[int] = None,
                  share_prefix: bool = False, no_repeat_ngram_size: Optional[int] = None, bad_words_ids=None, suppress_tokens=None,
-                 min_new_tokens: Optional[int] = None, min_length: Optional[int] = None, **kwargs):
+                 min_new_tokens: Optional[int] = None, min_length: Optional[int] = None, allowed_continuations=None, **kwargs):
         """Greedy / temperature sampling loop with the semantics of HF 4.29.2 ``generate`` driven by
         :meth:`prepare_inputs_for_generation`: the full prompt (with audio) once, then one token per step
         against the engine's KV cache; ``stopping_criteria`` are called as ``c(ids, scores)`` each step
@@ -413,10 +414,23 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
         repetition penalty (HF: after); a -inf stays -inf under the penalty and changes no other token, so the distribution is the
         same.  Under beams the banned tokens still count in the log-softmax and are only left out of the candidates, as in HF.
         ``min_length`` counts the row's own length.  ``return_logprobs`` stays the model's distribution over the raw logits.  With all
-        of them off (``None``, ``0``, empty) nothing is launched or allocated for them."""
+        of them off (``None``, ``0``, empty) nothing is launched or allocated for them.
+
+        ``allowed_continuations`` (HF 4.29.2's ``prefix_allowed_tokens_fn`` with the set given as data; :mod:`llark_amd.m2t.guide`): one
+        choice set -- a non-empty list of non-empty token-id sequences -- for every row, or a list with one set (or None: an
+        unconstrained row) per row.  Every row's new tokens are then one of its sequences followed by EOS (a valid label every time,
+        in one pass); one ``ops.guide_rows`` launch per step, after the constraints and before the choice, on every path: greedy,
+        device sampler, ``torch.multinomial``, padded batches and beams.  It needs an EOS token.  Under beams a token outside the set
+        still counts in the log-softmax: with ``num_beams`` >= the set's size and ``length_penalty=0`` the result is the sequence with
+        the highest summed log-probability, what ``score_continuations(...).sum()`` ranks first.  ``return_logprobs`` stays the model's
+        distribution over the raw logits.  None: nothing is launched or allocated."""
         if num_beam_groups is not None and num_beam_groups != 1:
             raise NotImplementedError(f"num_beam_groups={num_beam_groups!r}: diverse beam groups are not implemented")
         constraints = constraints_from_generate(no_repeat_ngram_size, bad_words_ids, suppress_tokens, min_new_tokens, min_length)
+        guide, choice = guide_from_generate(allowed_continuations, input_ids.shape[0])
+        if guide is not None:
+            require_eos(eos_token_id if eos_token_id is not None else getattr(self.generation_config, "eos_token_id", None))
+        guided = {} if guide is None else dict(guide=guide, choice=choice)
         if num_beams is not None and num_beams != 1:
             if do_sample:
                 raise NotImplementedError("do_sample=True with num_beams > 1 (beam sampling) is not implemented")
@@ -424,7 +438,7 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
                 raise NotImplementedError("repetition_penalty with num_beams > 1 is not implemented (no logits processors under beams)")
             return self._generate_beam(input_ids, attention_mask, audio_encodings, max_new_tokens, stopping_criteria, eos_token_id,
                                        num_beams, length_penalty, early_stopping, num_return_sequences, return_logprobs, share_prefix,
-                                       constraints)
+                                       constraints, **guided)
         sampling = params_from_generate(do_sample, temperature, top_k, top_p, repetition_penalty, seed)
         eng = self.engine
         eos = eos_token_id if eos_token_id is not None else getattr(self.generation_config, "eos_token_id", None)
@@ -433,6 +447,8 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
         use_eos = eos is not None and eos >= 0
 
         def draw(rows):
+            if guide is not None:                  # a row left without a finite logit draws any token; finish() raises for it by name
+                rows = torch.where(torch.isneginf(rows).all(-1, keepdim=True), torch.zeros_like(rows), rows)
             return torch.multinomial(torch.softmax(rows / max(temperature, 1e-6), dim=-1), 1)
         choose = draw if do_sample and sampling is None else None                             # do_sample with temperature alone
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
@@ -440,13 +456,14 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
             segs = plan_splice_on(eng.device, packed, audio_encodings, self.model.audio_encoder_config)
             return generate_padded(eng, rows, segs, input_ids, *((int(eos), int(pad)) if use_eos else (-1, 0)), max_new_tokens,
                                    stopping_criteria, sampling=sampling, constraints=constraints, return_logprobs=return_logprobs,
-                                   choose=choose)
+                                   choose=choose, **guided)
         choose = choose or (lambda rows: rows.argmax(-1, keepdim=True))
         ids = input_ids.to(eng.device)
         chooser = TokenChooser.build(ids.shape[0], eng.dims.vocab_size, ids.device, sampling=sampling, constraints=constraints,
-                                     history_len=ids.shape[1] + max_new_tokens, eos=eos, choose=choose)
+                                     history_len=ids.shape[1] + max_new_tokens, eos=eos, choose=choose,
+                                     **({} if guide is None else dict(guide=guide)))
         if chooser is not None:
-            chooser.admit(range(ids.shape[0]), list(input_ids))
+            chooser.admit(range(ids.shape[0]), list(input_ids), **({} if guide is None else dict(choice=choice)))
         unfinished = torch.ones((ids.shape[0], 1), dtype=torch.bool, device=ids.device)      # HF: unfinished_sequences, per row
         past = None
         lps = []
@@ -479,7 +496,8 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
         return ids
 
     def _generate_beam(self, input_ids, attention_mask, audio_encodings, max_new_tokens, stopping_criteria, eos_token_id, num_beams,
-                       length_penalty, early_stopping, num_return_sequences, return_logprobs, share_prefix, constraints=None):
+                       length_penalty, early_stopping, num_return_sequences, return_logprobs, share_prefix, constraints=None, guide=None,
+                       choice=None):
         """generate(num_beams > 1): example b is the sequence input_ids[b][mask[b]] (all of it without a mask), prefilled once into
         slot b * num_beams and cloned into the example's other slots; then one engine.beam_step per token.  Returns HF's layout."""
         eng = self.engine
@@ -504,6 +522,9 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
             beam.constraints = DeviceConstraints(constraints, N * B, scores.shape[-1], max(lens) + max_new_tokens, eng.device,
                                                  eos if use_eos else None)
             beam.constraints.admit(range(N * B), [rows[s // B] for s in range(N * B)])
+        if guide is not None:                                                      # every beam of an example starts at its set's root
+            beam.guide = DeviceGuide(guide, N * B, scores.shape[-1], eng.device, eos if use_eos else None)
+            beam.guide.admit(range(N * B), [choice[s // B] for s in range(N * B)])
         if getattr(self, "beam_observer", None) is not None:                       # tests: install the BeamSearch hooks before the first step
             self.beam_observer(beam, eng)
         scores = scores.repeat_interleave(B, dim=0)
@@ -524,6 +545,8 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
             n += 1
         if beam.constraints is not None:
             beam.constraints.check()
+        if beam.guide is not None:
+            beam.guide.check(off_set=False)
         ids, lps, _ = beam.finalize(input_ids, max_new_tokens, R)
         return (ids, lps) if return_logprobs else ids
 

@@ -30,6 +30,7 @@ from .choice import TokenChooser, generate_padded, unpack_prompts
 from .llamav2 import EngineCache, plan_splice_on
 from .mpt_engine import HipMptEngine, MptDims
 from .constraints import constraints_from_generate
+from .guide import guide_from_generate, require_eos
 from .sampling import params_from_generate
 from .special_tokens import DEFAULT_AUDIO_END_TOKEN, DEFAULT_AUDIO_PATCH_TOKEN, DEFAULT_AUDIO_START_TOKEN
 
@@ -297,7 +298,8 @@ class WrappedMPTForCausalLM(nn.Module):
                  attention_mask=None, pad_token_id=None, do_sample: bool = False, temperature: float = 1.0, top_k: Optional[int] = None,
                  top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, seed: Optional[int] = None,
                  return_logprobs: bool = False, num_beams: Optional[int] = None, no_repeat_ngram_size: Optional[int] = None,
-                 bad_words_ids=None, suppress_tokens=None, min_new_tokens: Optional[int] = None, min_length: Optional[int] = None, **kwargs):
+                 bad_words_ids=None, suppress_tokens=None, min_new_tokens: Optional[int] = None, min_length: Optional[int] = None,
+                 allowed_continuations=None, **kwargs):
         """Generation loop driven by :meth:`prepare_inputs_for_generation` (prompt with audio once, then one token per step).  An
         ``attention_mask`` with zeros (left- or right-padded) runs every row as if it were alone on the engine's ragged slot mode
         (:func:`llark_amd.m2t.choice.generate_padded`); ``None`` or all ones takes this uniform path and never enters the slot mode.
@@ -316,10 +318,21 @@ class WrappedMPTForCausalLM(nn.Module):
         choice, greedy or sampled, uniform or padded, from each row's history on the device (its own prompt without padding, then what
         it generated).  The ban comes BEFORE the repetition penalty (HF: after): a -inf stays -inf under the penalty and changes no
         other token, so the distribution is the same.  ``min_length`` counts the row's own length; ``return_logprobs`` stays the
-        model's distribution over the raw logits.  All off (``None``, ``0``, empty): nothing is launched or allocated for them."""
+        model's distribution over the raw logits.  All off (``None``, ``0``, empty): nothing is launched or allocated for them.
+
+        ``allowed_continuations`` (HF 4.29.2's ``prefix_allowed_tokens_fn`` with the set given as data; :mod:`llark_amd.m2t.guide`): one
+        choice set -- a non-empty list of non-empty token-id sequences -- for every row, or a list with one set (or None: an
+        unconstrained row) per row.  Every row's new tokens are then one of its sequences followed by ``eos_token_id``, which it
+        needs; one ``ops.guide_rows`` launch per step, after the constraints and before the choice, greedy or sampled, uniform or
+        padded.  On the uniform path a row that emitted EOS keeps emitting it until every row has.  None: nothing is launched or
+        allocated."""
         if num_beams is not None and num_beams != 1:
             raise NotImplementedError(f"num_beams={num_beams!r}: beam search is not implemented for MPT (no K/V fork path there yet)")
         constraints = constraints_from_generate(no_repeat_ngram_size, bad_words_ids, suppress_tokens, min_new_tokens, min_length)
+        guide, choice = guide_from_generate(allowed_continuations, input_ids.shape[0])
+        if guide is not None:
+            require_eos(eos_token_id)
+        guided = {} if guide is None else dict(guide=guide, choice=choice)
         sampling = params_from_generate(do_sample, temperature, top_k, top_p, repetition_penalty, seed, always=bool(do_sample))
         eng = self.engine
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
@@ -330,15 +343,16 @@ class WrappedMPTForCausalLM(nn.Module):
             use_eos = eos_token_id is not None and eos_token_id >= 0
             eos_k, pad_k = (int(eos_token_id), int(eos_token_id if pad_token_id is None else pad_token_id)) if use_eos else (-1, 0)
             return generate_padded(eng, rows, segs, input_ids, eos_k, pad_k, max_new_tokens, stopping_criteria, sampling=sampling,
-                                   constraints=constraints, return_logprobs=return_logprobs)
+                                   constraints=constraints, return_logprobs=return_logprobs, **guided)
         ids = input_ids.to(eng.device)
 
         def choose(rows):
             return rows.argmax(-1, keepdim=True)
         chooser = TokenChooser.build(ids.shape[0], eng.dims.vocab_size, ids.device, sampling=sampling, constraints=constraints,
-                                     history_len=ids.shape[1] + max_new_tokens, eos=eos_token_id, choose=choose)
+                                     history_len=ids.shape[1] + max_new_tokens, eos=eos_token_id, choose=choose,
+                                     **({} if guide is None else dict(guide=guide)))
         if chooser is not None:
-            chooser.admit(range(ids.shape[0]), list(input_ids))
+            chooser.admit(range(ids.shape[0]), list(input_ids), **({} if guide is None else dict(choice=choice)))
         past = None
         lps = []
         for _ in range(max_new_tokens):

@@ -1280,13 +1280,62 @@ def constrain_rows(logits: torch.Tensor, *, vocab: Optional[int] = None, state: 
           "constrain_rows")
 
 
+GUIDE_MAX_VOCAB = 65536               # caps of llark_guide_rows (csrc/guide.hip)
+GUIDE_MAX_NODES = 1 << 20
+GUIDE_MAX_EDGES = 1 << 20
+GUIDE_FREE, GUIDE_CLOSED = -1, -2     # node values: an unconstrained slot; only eos is allowed
+GUIDE_STATUS_OFF_SET = 2              # bit 1 of the status word: a slot was handed a token outside its set
+GUIDE_STATUS_EMPTY = 4                # bit 2: a row had no allowed token with a finite logit
+
+
+def guide_rows(logits: torch.Tensor, child_off: torch.Tensor, child_tok: torch.Tensor, child_node: torch.Tensor, terminal: torch.Tensor,
+               node_in: torch.Tensor, node_out: torch.Tensor, *, eos: int, vocab: Optional[int] = None,
+               state: Optional[torch.Tensor] = None, slot_of_row: Optional[torch.Tensor] = None, parent: Optional[torch.Tensor] = None,
+               last_token: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, ban: Optional[torch.Tensor] = None,
+               ban_accumulate: bool = False, n_open: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None) -> None:
+    """The tokens with which every row of fp32 ``logits`` [rows, >= vocab] may continue inside its slot's closed set of sequences, in one
+    launch: the prefix tree ``child_off`` (int32 [nodes + 1]) / ``child_tok`` / ``child_node`` (int32 [edges]) / ``terminal`` (int32
+    [nodes]) and the slots' nodes ``node_in`` (read) / ``node_out`` (written; the caller swaps the two), GUIDE_FREE: unconstrained,
+    GUIDE_CLOSED: only ``eos``.  A slot first takes the node of its ``parent`` entry (int32 [slots], any element stride) and steps it by
+    ``last_token[slot]`` (int64 [slots]; None: prefill rows, no step).  ``out`` (fp32 [rows, >= vocab]; may be ``logits`` itself)
+    receives the raw bits at allowed columns and -inf elsewhere, ``ban`` (int32 [slots, >= ceil(vocab / 32)]) the bitmap of what is
+    NOT allowed, OR-ed into its content with ``ban_accumulate``, ``n_open`` (int32 [rows]) the allowed columns with a finite or +inf
+    logit; ``status`` (int32 [1]) collects GUIDE_STATUS_*.  Row r belongs to slot ``slot_of_row[r]`` (identity without it); with
+    ``state`` only ROW_ACTIVE slots are touched.  Contract: include/llark_hip.h (llark_guide_rows)."""
+    i32, f32 = torch.int32, torch.float32
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    rows = logits.shape[0]
+    vocab = logits.shape[1] if vocab is None else int(vocab)
+    assert 0 < vocab <= logits.shape[1]
+    slots = node_in.numel()
+    n_nodes, n_edges = terminal.numel(), child_tok.numel()
+    assert node_out.numel() == slots and node_in.data_ptr() != node_out.data_ptr()
+    assert child_off.numel() == n_nodes + 1 and child_node.numel() == n_edges
+    assert all(t is None or t.numel() == slots for t in (state, last_token))
+    assert parent is None or (parent.dim() == 1 and parent.shape[0] == slots)
+    assert ban is None or (ban.dim() == 2 and ban.shape[0] == slots and ban.stride(1) == 1)
+    assert out is None or (out.dim() == 2 and out.shape[0] == rows and out.stride(1) == 1 and out.shape[1] >= vocab)
+    assert all(t is None or t.numel() == rows for t in (slot_of_row, n_open)) and (status is None or status.numel() == 1)
+    check(_lib.lib().llark_guide_rows(_dev(logits, "logits", f32, contiguous=False), logits.stride(0), vocab, rows, slots,
+                                      _opt(state, "state", i32), _opt(slot_of_row, "slot_of_row", i32), _dev(child_off, "child_off", i32),
+                                      _opt(child_tok, "child_tok", i32) if n_edges else None,
+                                      _opt(child_node, "child_node", i32) if n_edges else None, _dev(terminal, "terminal", i32), n_nodes,
+                                      n_edges, _dev(node_in, "node_in", i32), _dev(node_out, "node_out", i32),
+                                      _opt(parent, "parent", i32, contiguous=False), parent.stride(0) if parent is not None else 1,
+                                      _opt(last_token, "last_token", torch.int64), int(eos), _opt(out, "out", f32, contiguous=False),
+                                      _ld(out), _opt(ban, "ban", i32, contiguous=False), _ld(ban), int(bool(ban_accumulate)),
+                                      _opt(n_open, "n_open", i32), _opt(status, "status", i32), _stream()), "guide_rows")
+
+
 def beam_advance(cand_score: torch.Tensor, cand_token: torch.Tensor, cand_logprob: torch.Tensor, n_examples: int, beams: int, step: int,
                  eos: int, pad: int, length_penalty: float, early_stopping: bool, score: torch.Tensor, rank_of_slot: torch.Tensor,
                  state: torch.Tensor, pos_rows: Optional[torch.Tensor], cur_len: torch.Tensor, next_ids: torch.Tensor, heap: torch.Tensor,
-                 heap_meta: torch.Tensor, done: torch.Tensor, trellis: torch.Tensor, pairs: torch.Tensor, pair_count: torch.Tensor) -> None:
+                 heap_meta: torch.Tensor, done: torch.Tensor, trellis: torch.Tensor, pairs: torch.Tensor, pair_count: torch.Tensor,
+                 open: bool = False) -> None:
     """One beam-search step of every example from the sorted candidates of its ``beams`` slots (:func:`beam_topk_rows`, row = slot): the
     next beams and their slots, the finished-hypothesis heap, the done flags, row ``step`` of the trellis and the K/V copy list, all on the
-    device.  Shapes and rules: include/llark_hip.h (llark_beam_advance)."""
+    device.  ``open``: an example goes on while it has ANY live beam (a search inside a closed set; llark_beam_advance_open).  Shapes and
+    rules: include/llark_hip.h (llark_beam_advance)."""
     i32, f32 = torch.int32, torch.float32
     slots = n_examples * beams
     assert all(t.numel() == slots * 2 * beams for t in (cand_score, cand_token, cand_logprob))
@@ -1294,13 +1343,14 @@ def beam_advance(cand_score: torch.Tensor, cand_token: torch.Tensor, cand_logpro
     assert cur_len.numel() == n_examples and done.numel() == n_examples and pair_count.numel() == n_examples
     assert heap.numel() == slots * BEAM_HEAP_STRIDE and heap_meta.numel() == n_examples * BEAM_META_STRIDE
     assert trellis.dim() == 3 and trellis.shape[1:] == (slots, 3) and pairs.numel() == n_examples * max(beams - 1, 1) * 2
-    check(_lib.lib().llark_beam_advance(_dev(cand_score, "cand_score", f32), _dev(cand_token, "cand_token", i32),
-                                        _dev(cand_logprob, "cand_logprob", f32), int(n_examples), int(beams), int(step), trellis.shape[0],
-                                        int(eos), int(pad), float(length_penalty), int(bool(early_stopping)), _dev(score, "score", f32),
-                                        _dev(rank_of_slot, "rank_of_slot", i32), _dev(state, "state", i32), _opt(pos_rows, "pos_rows", i32),
-                                        _dev(cur_len, "cur_len", i32), _dev(next_ids, "next_ids", torch.int64), _dev(heap, "heap", i32),
-                                        _dev(heap_meta, "heap_meta", i32), _dev(done, "done", i32), _dev(trellis, "trellis", i32),
-                                        _dev(pairs, "pairs", i32), _dev(pair_count, "pair_count", i32), _stream()), "beam_advance")
+    L = _lib.lib()
+    entry = L.llark_beam_advance_open if open else L.llark_beam_advance
+    check(entry(_dev(cand_score, "cand_score", f32), _dev(cand_token, "cand_token", i32), _dev(cand_logprob, "cand_logprob", f32),
+                int(n_examples), int(beams), int(step), trellis.shape[0], int(eos), int(pad), float(length_penalty),
+                int(bool(early_stopping)), _dev(score, "score", f32), _dev(rank_of_slot, "rank_of_slot", i32), _dev(state, "state", i32),
+                _opt(pos_rows, "pos_rows", i32), _dev(cur_len, "cur_len", i32), _dev(next_ids, "next_ids", torch.int64),
+                _dev(heap, "heap", i32), _dev(heap_meta, "heap_meta", i32), _dev(done, "done", i32), _dev(trellis, "trellis", i32),
+                _dev(pairs, "pairs", i32), _dev(pair_count, "pair_count", i32), _stream()), "beam_advance")
 
 
 def kv_copy_slots(k_cache: torch.Tensor, vt_cache: torch.Tensor, pairs: torch.Tensor, count: torch.Tensor, p0: torch.Tensor,

@@ -38,6 +38,12 @@ Greedy against constrained greedy, same run and same block scheme: the second ki
 (ops.constrain_rows under no_repeat_ngram_size 3, two bad words and min_new_tokens; the histories live on the device) and picks its
 token from them with ops.sample_rows(do_sample=False), two more launches per step, as EngineSlots(constraints=...) does.  ONE JSON line,
 also written to --out.
+
+    python scripts/bench_generate_inflight.py --guided [--slots 16,64] [--out profiles/bench_generate_inflight_guided.json]
+Greedy against guided greedy, same run and same block scheme: the second kind's step sets -inf outside the slot's choice set
+(ops.guide_rows; 24 sequences long enough that every slot stays inside the tree for the whole run, the nodes live on the device) and picks
+its token with ops.sample_rows(do_sample=False), two more launches per step, as EngineSlots(choice_sets=...) does.  ONE JSON line, also
+written to --out.
 """
 import argparse
 import json
@@ -424,16 +430,75 @@ def main_constraints(args, slot_list):
     print(json.dumps(res), flush=True)
 
 
+def main_guided(args, slot_list):
+    import statistics
+
+    from llark_amd.m2t.choice import TokenChooser
+    from llark_amd.m2t.guide import ChoiceSets
+    steps, blocks = 16, 8
+    examples = make_examples(64, args.seed)
+    max_seq = max(ids.numel() for ids, _, _ in examples) + 8 + steps * (2 * blocks + 2)
+    model = RandomLlama(args.precision, max(slot_list), max_seq)
+    eng = model.engine
+    n_seq, length = 24, steps * (blocks + 1) + 8                 # longer than the guided steps of a run: no slot reaches a leaf
+    g = torch.Generator().manual_seed(args.seed)
+    res = {"bench": "generate_inflight_guided", "model": "llama2-7b dims, random weights", "precision": args.precision,
+           "choice_set": dict(sequences=n_seq, length=length, eos=2), "steps_per_block": steps, "blocks": blocks, "slots": {}}
+    for n in slot_list:
+        eng.init_slots(n)
+        rows = [examples[i % len(examples)] for i in range(n)]
+        logits = eng.prefill_slots([r[0].cuda() for r in rows], [(k, 1, r[1].cuda()) for k, r in enumerate(rows)], range(n))
+        vocab = logits.shape[-1]
+        first = torch.randint(3, vocab, (6,), generator=g).tolist()          # six first tokens: the root and the next nodes fan out
+        seqs = [[first[i % 6], 3 + i % 4] + torch.randint(3, vocab, (length - 2,), generator=g).tolist() for i in range(n_seq)]
+        chooser = TokenChooser(n, vocab, eng.device, guide=ChoiceSets([seqs]), eos=2)
+        chooser.admit(range(n), [r[0] for r in rows], choice=[0] * n)        # greedy on the guided rows: one guide_rows + one sample_rows launch
+        kinds = {"greedy": None, "guided": lambda lg: chooser(lg, state=eng.slot_state)}
+        ids = chooser(logits, state=eng.slot_state)
+
+        def block(kind):                                         # a node follows the guided blocks' tokens only: the timing is the point
+            nonlocal ids
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                ids, _, _ = eng.decode_slots(ids, sample=kinds[kind])
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / steps * 1e3
+
+        block("greedy"), block("guided")                         # warm
+        ms = {"greedy": [], "guided": []}
+        for b in range(blocks):
+            for kind in (("greedy", "guided") if b % 2 == 0 else ("guided", "greedy")):
+                ms[kind].append(block(kind))
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        chooser.finish()
+        assert int(chooser.guide.node.min()) >= 0, "a slot left the tree: the timing is not of guided steps"
+        cell = {"greedy_step_ms": round(med["greedy"], 4), "guided_step_ms": round(med["guided"], 4),
+                "greedy_min_max_ms": [round(min(ms["greedy"]), 4), round(max(ms["greedy"]), 4)],
+                "guided_min_max_ms": [round(min(ms["guided"]), 4), round(max(ms["guided"]), 4)],
+                "excess_fraction_of_step": round(med["guided"] / med["greedy"] - 1.0, 4)}
+        res["slots"][str(n)] = cell
+        print(json.dumps({str(n): cell}), file=sys.stderr, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--guided", action="store_true", help="same-run A/B of the decode step with every slot active: greedy against greedy "
+                    "inside a choice set of 24 sequences (default slot counts 16,64)")
     ap.add_argument("--constraints", action="store_true", help="same-run A/B of the decode step with every slot active: greedy against greedy "
                     "under no_repeat_ngram_size 3, two bad words and min_new_tokens (default slot counts 16,64)")
     ap.add_argument("--sampling", action="store_true", help="same-run A/B of the decode step with every slot active: greedy against the "
                     "device sampler (default slot counts 16,64)")
     ap.add_argument("--logprobs", action="store_true", help="same-run A/B of the decode step with every slot active: greedy against greedy + "
                     "token log-probabilities (default slot counts 16,64)")
-    ap.add_argument("--out", default=None, help="with --logprobs / --constraints: also write the JSON here (default "
-                    "profiles/bench_generate_inflight_logprobs.json / profiles/bench_generate_inflight_constraints.json)")
+    ap.add_argument("--out", default=None, help="with --logprobs / --constraints / --guided: also write the JSON here (default "
+                    "profiles/bench_generate_inflight_logprobs.json / ..._constraints.json / ..._guided.json)")
     ap.add_argument("--questions-per-clip", default=None, help="e.g. 1,4,8: consecutive examples share an encoding, an audio-first prefix "
                     "and a prefix key (inflight schedule only; one result cell per slot count and value)")
     ap.add_argument("--share-prefix", action="store_true", help="with --questions-per-clip: run every cell with share_prefix off and on")
@@ -458,6 +523,10 @@ def main():
         if args.out is None:
             args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "bench_generate_inflight_constraints.json")
         return main_constraints(args, [16, 64] if args.slots == ap.get_default("slots") else slot_list)
+    if args.guided:
+        if args.out is None:
+            args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "bench_generate_inflight_guided.json")
+        return main_guided(args, [16, 64] if args.slots == ap.get_default("slots") else slot_list)
     if args.questions_per_clip:
         return main_shared(args, slot_list)
     if args.share_prefix:
