@@ -555,6 +555,47 @@ int llark_attn_decode_rope_bf16_rows(const float* qkv, int batch, int nh, int hd
                                      int smax, void* out, void* out_lo, const float* alibi_slopes, llark_stream_t stream);
 int llark_decode_advance_rows(const float* logits, int ldl, int vocab, int batch, const int64_t* choice, int* pos_rows, int* state,
                               int64_t* next_ids, int64_t* out_col, int ld_out, int64_t eos, int64_t pad, llark_stream_t stream);
+/* Speculative greedy decoding: a decode step that verifies a block of drafted tokens per slot (csrc/attn_block.hip, csrc/speculate.hip).
+ *   llark_attn_decode_rope_bf16_block: llark_attn_decode_rope_bf16_rows for rows that belong to the SAME slot at consecutive positions.
+ *     qkv fp32 [n_slots * stride][3 * nh * 128], stride 1 .. 8 rows per slot; blk int32 [n_slots] (0 .. stride; larger counts as stride)
+ *     and pos_rows int32 [n_slots] on the device.  Slot b owns rows b*stride .. b*stride + blk[b] - 1; row i is the token at position
+ *     pos_rows[b] + i.  Workgroup (head, slot) rotates and appends the K / V of all its rows first (rope_split's arithmetic and rounding),
+ *     then walks the cache once; query i sees keys 0 .. pos_rows[b] + i.  out (+ out_lo) bf16 [n_slots * stride][nh * 128].
+ *     A slot with blk == 0 or pos < 0 writes nothing to the caches; a row at a position >= smax writes nothing; the output heads of such
+ *     rows and of rows >= blk[b] are zero.  No ALiBi.  Contract: the out planes of row i and the cache rows written are BIT-equal to
+ *     what blk[b] successive llark_attn_decode_rope_bf16_rows launches with batch = n_slots produce (row i in launch i, slots whose
+ *     block is shorter idle).  16 waves per workgroup while nh * n_slots < 256, 4 otherwise, as llark_attn_decode_rope_bf16_rows.
+ *     Dynamic LDS holds stride * smax scores: above 128 KiB LLARK_ERR_UNSUPPORTED, before any launch.  LLARK_ERR_INVALID before any
+ *     launch: a null pointer, one lo plane only, hd != 128, stride outside 1 .. 8, smax % 8 != 0, smax > max_pos.
+ *   llark_spec_verify_rows: the bookkeeping after the logits of a block step, one launch, one workgroup per slot.  logits fp32
+ *     [n_slots * stride][ldl], ids int64 [n_slots * stride] (the block's input tokens), blk / state / pos_rows / budget int32 [n_slots]
+ *     (budget: tokens the slot may still emit).  For a slot that is LLARK_ROW_ACTIVE with blk > 0 and budget > 0:
+ *       g_i = first maximal index of logits row i over [0, vocab), a NaN counting as the maximum (llark_decode_advance_rows' rules);
+ *       a = number of leading i in 0 .. blk-2 with ids[i + 1] == g_i; the emitted tokens are g_0 .. g_a, cut at `budget` and after the
+ *       first eos (eos >= 0); n = their count (>= 1).
+ *     It writes out_tokens[b][0 .. 8) (int64, the emitted tokens, then pad), n_out[b] = n (int64, so that out_tokens and n_out can be
+ *     two views of one buffer and leave in one transfer), next_ids[b] = the last emitted token, pos_rows[b] += n, budget[b] -= n,
+ *     state[b] = LLARK_ROW_FINISHED when the run ended on eos, and appends the emitted tokens to hist[b][hist_len[b] ..] (int64
+ *     [n_slots][ld_hist], hist_len int32 [n_slots]; tokens beyond ld_hist are dropped; hist and hist_len may both be NULL).
+ *     Every other slot: out_tokens[b] = pad, n_out[b] = 0, nothing else is touched.
+ *   llark_spec_draft_rows: fills the next block, one launch.  A slot that is not ACTIVE, has pos_rows < 0, budget <= 0 or pos_rows >=
+ *     smax gets blk = 0 and pad ids.  Otherwise ids[b*stride] = next_ids[b], followed by n_draft drafted tokens and pad, and blk[b] =
+ *     1 + n_draft with n_draft <= k_max, blk <= stride, blk <= budget and pos_rows + blk <= smax.  The drafts are
+ *       drafts != NULL: drafts[b][0 .. n_drafts[b]) of the caller's int64 [n_slots][ld_drafts];
+ *       drafts == NULL (prompt lookup): for g = g_max down to 1, the first g for which the last g tokens of the slot's history occur
+ *       at an earlier start s <= hist_len - g - 1; of these the largest s; the tokens hist[s + g .. hist_len) that follow it (the
+ *       continuation may run into the suffix itself).  No match, or a history shorter than g + 1 for every g: n_draft = 0, a plain step.
+ *     LLARK_ERR_INVALID before any launch: a null pointer, neither drafts nor hist, stride outside 1 .. 8, k_max outside 0 .. 7, g_max
+ *     outside 1 .. 64. */
+int llark_attn_decode_rope_bf16_block(const float* qkv, int n_slots, int stride, int nh, int hd, const int* blk, const int* pos_rows,
+                                      const float* cos_t, const float* sin_t, int max_pos, void* k_cache, void* vt_cache, void* k_cache_lo,
+                                      void* vt_cache_lo, int smax, void* out, void* out_lo, llark_stream_t stream);
+int llark_spec_verify_rows(const float* logits, int ldl, int vocab, int n_slots, int stride, const int64_t* ids, const int* blk, int* state,
+                           int* pos_rows, int* budget, int64_t eos, int64_t pad, int64_t* out_tokens, int64_t* n_out, int64_t* next_ids,
+                           int64_t* hist, int* hist_len, int ld_hist, llark_stream_t stream);
+int llark_spec_draft_rows(const int64_t* next_ids, const int* state, const int* pos_rows, const int* budget, const int64_t* hist,
+                          const int* hist_len, int ld_hist, int n_slots, int stride, int k_max, int g_max, int smax, const int64_t* drafts,
+                          const int* n_drafts, int ld_drafts, int64_t* ids, int* blk, int64_t pad, llark_stream_t stream);
 /* Token sampling on the device (csrc/sample.hip): the producer of llark_decode_advance_rows' `choice`.
  *   llark_sample_rows: one workgroup per row r of logits fp32 [rows][ldl] (columns >= vocab are never read).  slot = slot_of_row[r]
  *     (int32 [rows], NULL: slot = r; rows map to DISTINCT slots); a row whose slot is outside [0, slots) or, when state != NULL (int32

@@ -419,7 +419,7 @@ class HipLlamaEngine:
         return False
 
     # ---- forward: decode ---------------------------------------------------------------------------
-    def _decode_layers(self, ws, batch: int, pos0: int, n_layers: int, pos_dev, hidden_sink, slot0: int, pos_rows) -> bool:
+    def _decode_layers(self, ws, batch: int, pos0: int, n_layers: int, pos_dev, hidden_sink, slot0: int, pos_rows, block=None) -> bool:
         """The decoder layers of a decode step.  Decided once, here: `fused` (o_proj / down_proj carry the FOLLOWING RMSNorm in their
         launch), `norm_a` (RMSNorm inside the consuming weight-streaming GEMM) and the attention form -- "rows" (ragged: each slot at its
         own position), "rope" (RoPE + cache append inside the attention launch), "dpos" (position in device memory, graph-capturable)
@@ -427,18 +427,21 @@ class HipLlamaEngine:
         ops.gemm16_mid, the weight-streaming GEMM for that row count; every other case keeps ops.gemm16."""
         d = self.dims
         H, I, nh, hd, eps, sp = d.hidden_size, d.intermediate_size, d.num_attention_heads, d.head_dim, d.rms_norm_eps, self.split
+        # block: (stride, blk) of a block step (decode_block) -- `batch` rows are n_slots * stride, slot b owns rows b*stride .. at
+        # consecutive positions, the caches belong to the n_slots slots; the decisions are those of the plain step at n_slots rows
+        n_cache = batch if block is None else batch // block[0]
         fused = batch <= 16 and n_layers > 0 and self.fuse_decode_norm and H <= 8192 and hidden_sink is None
-        norm_a = batch <= 16 and not fused and H % 32 == 0 and self._norm_gemm_takes(batch, 3 * H)
+        norm_a = batch <= 16 and not fused and H % 32 == 0 and self._norm_gemm_takes(n_cache, 3 * H)
         if fused:
             ops.rmsnorm_bf16(ws["h"], self.layers[0].ln1, eps, ws["x16"], ws["x16_lo"])
         if (self.decode_chain and batch == 1 and norm_a and self.fuse_decode_rope and pos_dev is None and hidden_sink is None
                 and not fused and H <= 4096 and slot0 == 0 and pos_rows is None and not torch.cuda.is_current_stream_capturing()):
             self._decode_layers_chained(ws, pos0, n_layers)
             return False
-        attn = "rows" if pos_rows is not None else "rope" if self.fuse_decode_rope else "dpos" if pos_dev is not None else "plain"
+        attn = "block" if block is not None else "rows" if pos_rows is not None else "rope" if self.fuse_decode_rope else "dpos" if pos_dev is not None else "plain"
         if attn == "rows" and self._groups is not None and pos_rows is self.slot_len and ws.get("attn_shared") is not None:
             attn = "shared"                                   # share_prefix with at least one group: the slots of a clip read their prefix once
-        pos = pos_rows if attn in ("rows", "shared") else pos_dev if pos_dev is not None else pos0
+        pos = pos_rows if attn in ("rows", "shared", "block") else pos_dev if pos_dev is not None else pos0
         mid = ws["mid"] if pos_rows is not None and self._mid_step(ws, batch) else None      # 17 .. 64 slots: rmsnorm_bf16 + gemm16_mid
         epi_gu, cos, sin = self._epi_swiglu(), self.cos, self.sin
         h, qkv, x16, x16l, q, ql = ws["h"], ws["qkv"], ws["x16"], ws["x16_lo"], ws["q"], ws["q_lo"]
@@ -447,7 +450,7 @@ class HipLlamaEngine:
             L = self.layers[i]
             if hidden_sink is not None:                       # HF output_hidden_states: the stream as it ENTERS every layer
                 hidden_sink.append(h.view(batch, 1, H).clone())
-            kc, vc, kcl, vcl = self._kv_views(i, slot0, slot0 + batch)
+            kc, vc, kcl, vcl = self._kv_views(i, slot0, slot0 + n_cache)
             if norm_a:
                 ops.gemm16_rmsnorm_a(h, L.ln1, eps, L.wqkv, 3 * H, ops.EPI_F32, sp, c=qkv)
             else:
@@ -457,7 +460,9 @@ class HipLlamaEngine:
                     ops.gemm16_mid(x16, x16l, L.wqkv, None, 3 * H, ops.EPI_F32, mid, c=qkv)
                 else:
                     ops.gemm16(x16, x16l, L.wqkv, None, 3 * H, ops.EPI_F32, c=qkv)
-            if attn == "rows":
+            if attn == "block":
+                ops.attn_decode_rope_block(qkv, n_cache, block[0], nh, hd, block[1], pos, cos, sin, kc, vc, att, kcl, vcl, attl)
+            elif attn == "rows":
                 ops.attn_decode_rope_rows(qkv, batch, nh, hd, pos, cos, sin, kc, vc, att, kcl, vcl, attl)
             elif attn == "shared":
                 ops.attn_decode_rope_shared(qkv, batch, nh, hd, pos, cos, sin, kc, vc, att, self._groups, self._slot_shared, ws["attn_shared"],
@@ -711,6 +716,7 @@ class HipLlamaEngine:
 
     def _clear_slots(self) -> None:
         self.n_slots = 0
+        self._block_ws = None                                   # init_block_decode: the block step's workspace, per slot count
         self.slot_len = self.slot_state = None                 # device int32 [n_slots]: positions, ops.ROW_* states
         self.slot_len_host: List[int] = []
         self.slot_state_host: List[int] = []
@@ -738,7 +744,7 @@ class HipLlamaEngine:
             per_slot = d.num_hidden_layers * d.hidden_size * self.smax * 2 * 2 * (2 if self.split else 1)
             raise RuntimeError(f"init_slots({n_slots}): the KV cache does not fit: {per_slot / 2**30:.2f} GiB per slot x {n_slots} slots "
                                f"(max_seq {self.smax}, precision {self.precision!r}); use fewer slots or a smaller max_seq") from e
-        self.n_slots = n_slots
+        self.n_slots, self._block_ws = n_slots, None
         self.slot_len = torch.full((n_slots,), -1, dtype=torch.int32, device=self.device)
         self.slot_state = torch.full((n_slots,), ops.ROW_IDLE, dtype=torch.int32, device=self.device)
         self.slot_len_host, self.slot_state_host = [-1] * n_slots, [ops.ROW_IDLE] * n_slots
@@ -1019,6 +1025,89 @@ class HipLlamaEngine:
         normed = self._layers_forward(ws, n, 1, 0, pos_rows=self.slot_len)
         self._head(ws, logits, normed, may_fuse=True)
         return logits
+
+    # ---- speculative greedy decoding: a decode step over a block of rows per slot -------------------------------------------------
+    # Row 0 of slot b is the token the plain step would feed (at position slot_len[b]); rows 1 .. are drafted tokens at the following
+    # positions.  One pass over the weights gives the greedy token after every row; ops.spec_verify_rows keeps the drafts that equal
+    # them and emits one token more.  Rejected positions need no rollback: they lie beyond slot_len and are overwritten before they are
+    # read.  llark_amd.m2t.speculate holds the loop.
+    def init_block_decode(self, stride: int) -> None:
+        """Allocate the block step's own workspace: n_slots * stride <= 16 rows (the row count the m <= 16 decode Linears take)."""
+        n = self.n_slots
+        if n == 0:
+            raise RuntimeError("ragged mode is not active: call init_slots(n) first")
+        if not 1 <= stride <= ops.SPEC_MAX_BLOCK or n * stride > 16:
+            raise ValueError(f"block decode needs 1 <= stride <= {ops.SPEC_MAX_BLOCK} and n_slots * stride <= 16, got {n} slots x {stride}")
+        dev, i32, i64 = self.device, torch.int32, torch.int64
+        ws = self._alloc_workspace(n * stride, 1)
+        ws.update(stride=stride, logits=torch.empty((n * stride, self.dims.vocab_size), dtype=torch.float32, device=dev),
+                  ids=torch.zeros((n * stride,), dtype=i64, device=dev), blk=torch.zeros((n,), dtype=i32, device=dev),
+                  budget=torch.zeros((n,), dtype=i32, device=dev), next=torch.zeros((n,), dtype=i64, device=dev),
+                  step=ops.spec_step_buffer(n, dev), hist=torch.zeros((n, self.smax + 1), dtype=i64, device=dev),
+                  hist_len=torch.zeros((n,), dtype=i32, device=dev))
+        self._block_ws = ws
+
+    def start_block_decode(self, histories: Sequence[torch.Tensor], budgets: Sequence[int]) -> None:
+        """Every slot's history (prompt and the tokens emitted so far, the last of which the next step feeds) and the number of tokens
+        it may still emit."""
+        ws = self._block_ws
+        if len(histories) != self.n_slots or len(budgets) != self.n_slots:
+            raise ValueError(f"{self.n_slots} slots need as many histories and budgets")
+        hist = torch.zeros(ws["hist"].shape, dtype=torch.int64)
+        for b, r in enumerate(histories):
+            r = r.reshape(-1).to("cpu", torch.int64)
+            if not 1 <= r.numel() <= hist.shape[1]:
+                raise ValueError(f"slot {b}: a history of {r.numel()} tokens (1 .. max_seq + 1)")
+            hist[b, : r.numel()] = r
+        ws["hist"].copy_(hist)
+        ws["hist_len"].copy_(torch.tensor([int(r.numel()) for r in histories], dtype=torch.int32))
+        ws["next"].copy_(torch.tensor([int(r.reshape(-1)[-1]) for r in histories], dtype=torch.int64))
+        ws["budget"].copy_(torch.tensor([int(x) for x in budgets], dtype=torch.int32))
+
+    def decode_block(self, eos: int = -1, pad: int = 0, k_max: int = 1, g_max: int = 2, drafts: Optional[torch.Tensor] = None,
+                     n_drafts: Optional[torch.Tensor] = None) -> Tuple[List[List[int]], torch.Tensor, torch.Tensor]:
+        """One block step over all slots: draft (prompt lookup over the device history with suffixes of g_max .. 1 tokens, or
+        `drafts` int64 [n_slots][>= k_max] with `n_drafts` int32 [n_slots]) -> embedding -> the <= 16-row decode launch sequence with the
+        block attention -> final norm + lm_head -> verify.  Returns (the tokens each slot emitted, host lists; the block's input ids
+        [n_slots][stride] on the device; the fp32 logits [n_slots * stride][V], row b*stride + i being what token i of slot b was
+        chosen from -- buffers the next step overwrites).  One device-to-host transfer."""
+        ws, n = self._block_ws, self.n_slots
+        stride = ws["stride"]
+        if not 0 <= k_max < stride:
+            raise ValueError(f"k_max must be in 0 .. stride - 1 = {stride - 1}, got {k_max}")
+        ops.spec_draft_rows(ws["next"], self.slot_state, self.slot_len, ws["budget"], ws["ids"], ws["blk"], stride, k_max, self.smax,
+                            **(dict(hist=ws["hist"], hist_len=ws["hist_len"], g_max=g_max) if drafts is None else
+                               dict(drafts=drafts, n_drafts=n_drafts)), pad=max(pad, 0))
+        ops.embed_gather(ws["ids"], self.embed, ws["h"])
+        normed = self._decode_layers(ws, n * stride, 0, self.dims.num_hidden_layers, None, None, 0, self.slot_len, block=(stride, ws["blk"]))
+        self._head(ws, ws["logits"], normed, may_fuse=False)
+        out_tokens, n_out = ops.spec_step_views(ws["step"])
+        ops.spec_verify_rows(ws["logits"], ws["ids"], ws["blk"], self.slot_state, self.slot_len, ws["budget"], out_tokens, n_out, ws["next"],
+                             ws["hist"], ws["hist_len"], eos=eos, pad=pad)
+        toks, cnt = ops.spec_step_views(ws["step"].cpu())
+        emitted = []
+        for b in range(n):
+            k = int(cnt[b])
+            emitted.append(toks[b, :k].tolist())
+            if k:
+                self.slot_len_host[b] += k
+                if eos >= 0 and emitted[-1][-1] == eos:
+                    self.slot_state_host[b] = ops.ROW_FINISHED
+        return emitted, ws["ids"].view(n, stride), ws["logits"]
+
+    def truncate_slots(self, slots: Sequence[int], lens: Sequence[int]) -> None:
+        """Set slots back to shorter lengths, on the host and the device (after a host-side stop inside an accepted run): the positions
+        beyond are overwritten before they are read."""
+        slots = self._check_slots(slots)
+        lens = [int(x) for x in lens]
+        for b, x in zip(slots, lens):
+            if not 0 <= x <= self.slot_len_host[b]:
+                raise ValueError(f"slot {b}: cannot truncate length {self.slot_len_host[b]} to {x}")
+        if slots:
+            idx = torch.tensor(slots, dtype=torch.long, device=self.device)
+            self.slot_len[idx] = torch.tensor(lens, dtype=torch.int32, device=self.device)
+            for b, x in zip(slots, lens):
+                self.slot_len_host[b] = x
 
     def beam_step(self, ids: Optional[torch.Tensor], beam, logits: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, List[bool]]:
         """One beam-search step over all n_slots rows (beam: llark_amd.m2t.beam.BeamSearch, which owns example e's slots e * B ..):

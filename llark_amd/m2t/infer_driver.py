@@ -547,15 +547,19 @@ def infer_from_encodings(model, tokenizer, audio_encodings_dir: str, prompt: str
                          end_seq: Sequence[int], outfile: Optional[str] = None, batch_size: int = 8,
                          max_samples: Optional[int] = None, max_new_tokens: int = 512, audio_first: bool = True,
                          embed_dim: Optional[int] = None, num_beams: int = 1, length_penalty: float = 1.0,
-                         no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None) -> List[Dict[str, str]]:
+                         no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
+                         prompt_lookup_num_tokens: Optional[int] = None) -> List[Dict[str, str]]:
     """Directory of ``*.npy`` -> CSV, like ``scripts/inference/infer_from_encodings.py:main`` (same record fields; files
     in sorted order; ``example_id`` = path without ``.npy``).  Examples are grouped by frame count so that every batch
     shares one prompt length.  ``num_beams`` > 1: beam search with ``length_penalty``, one example per call (:func:`generate_beam`).
-    ``no_repeat_ngram_size`` / ``min_new_tokens`` go to ``model.generate`` on both paths (:mod:`llark_amd.m2t.constraints`)."""
+    ``no_repeat_ngram_size`` / ``min_new_tokens`` go to ``model.generate`` on both paths (:mod:`llark_amd.m2t.constraints`).
+    ``prompt_lookup_num_tokens`` K (1 .. 7; None or 0: off): speculative greedy decoding by prompt lookup
+    (:mod:`llark_amd.m2t.speculate`), ``batch_size * (K + 1) <= 16``; refused by ``generate`` next to beams or constraints."""
     from .constraints import constraints_from_generate
 
     constraints_from_generate(no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens)      # bad values raise here, by name
-    more = {k: v for k, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_new_tokens", min_new_tokens)) if v}
+    more = {k: v for k, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_new_tokens", min_new_tokens),
+                              ("prompt_lookup_num_tokens", prompt_lookup_num_tokens)) if v}
     if embed_dim is None:                                  # 4800 for Jukebox, 512 for CLAP (ModelArguments.mm_hidden_size)
         embed_dim = int(getattr(getattr(model, "config", None), "mm_hidden_size", EMBED_DIM))
     paths = sorted(glob.glob(os.path.join(audio_encodings_dir, "*.npy")))
@@ -748,6 +752,8 @@ def main(argv=None):
     ap.add_argument("--length_penalty", type=float, default=1.0, help="hypothesis score = sum of log-probabilities / length ** this")
     ap.add_argument("--no_repeat_ngram_size", type=int, default=0, help="no n-gram of this size occurs twice in prompt + completion; 0: off")
     ap.add_argument("--min_new_tokens", type=int, default=0, help="the EOS token is banned for this many new tokens; 0: off")
+    ap.add_argument("--prompt_lookup_num_tokens", type=int, default=0,
+                    help="speculative greedy decoding: verify this many tokens (1 .. 7) looked up in the row's own history per step; 0: off")
     for ignored in ("--ckpt-num", "--report_to", "--bf16", "--tf32", "--output_dir"):
         ap.add_argument(ignored, default=None, help="accepted for script compatibility")
     args = ap.parse_args(argv)
@@ -755,13 +761,18 @@ def main(argv=None):
 
     try:                                                   # before the model is loaded
         constraints_from_generate(no_repeat_ngram_size=args.no_repeat_ngram_size, min_new_tokens=args.min_new_tokens)
+        from .speculate import SpeculationParams
+        spec = SpeculationParams.from_generate(args.prompt_lookup_num_tokens)
+        if spec is not None:
+            spec.check_batch(args.batch_size)
     except ValueError as e:
         ap.error(str(e))
     model, tok, end_seq, mm_cfg = _load_for_inference(args, max(args.batch_size, args.num_beams))
     recs = infer_from_encodings(model, tok, args.audio_encodings_dir, args.prompt, mm_cfg, end_seq, outfile=args.outfile,
                                 batch_size=args.batch_size, max_samples=args.max_samples, max_new_tokens=args.max_new_tokens,
                                 num_beams=args.num_beams, length_penalty=args.length_penalty,
-                                **{k: v for k, v in (("no_repeat_ngram_size", args.no_repeat_ngram_size), ("min_new_tokens", args.min_new_tokens)) if v})
+                                **{k: v for k, v in (("no_repeat_ngram_size", args.no_repeat_ngram_size), ("min_new_tokens", args.min_new_tokens),
+                                                     ("prompt_lookup_num_tokens", args.prompt_lookup_num_tokens)) if v})
     print(f"writing {len(recs)} results to {args.outfile}")
     return recs
 

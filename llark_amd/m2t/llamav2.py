@@ -31,6 +31,7 @@ from .constraints import DeviceConstraints, constraints_from_generate
 from .guide import DeviceGuide, guide_from_generate, require_eos
 from .engine import HipLlamaEngine, LlamaDims
 from .sampling import params_from_generate
+from .speculate import SpeculationParams, generate_speculative
 from .special_tokens import DEFAULT_AUDIO_END_TOKEN, DEFAULT_AUDIO_PATCH_TOKEN, DEFAULT_AUDIO_START_TOKEN
 
 
@@ -383,7 +384,8 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
                  return_logprobs: bool = False, num_beams: Optional[int] = None, length_penalty: float = 1.0,
                  early_stopping: bool = False, num_return_sequences: Optional[int] = None, num_beam_groups: Optional[int] = None,
                  share_prefix: bool = False, no_repeat_ngram_size: Optional[int] = None, bad_words_ids=None, suppress_tokens=None,
-                 min_new_tokens: Optional[int] = None, min_length: Optional[int] = None, allowed_continuations=None, **kwargs):
+                 min_new_tokens: Optional[int] = None, min_length: Optional[int] = None, allowed_continuations=None,
+                 prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None, **kwargs):
         """Greedy / temperature sampling loop with the semantics of HF 4.29.2 ``generate`` driven by
         :meth:`prepare_inputs_for_generation`: the full prompt (with audio) once, then one token per step
         against the engine's KV cache; ``stopping_criteria`` are called as ``c(ids, scores)`` each step
@@ -423,9 +425,33 @@ class WrappedLlamav2ForCausalLM(LlamaForCausalLM):
         device sampler, ``torch.multinomial``, padded batches and beams.  It needs an EOS token.  Under beams a token outside the set
         still counts in the log-softmax: with ``num_beams`` >= the set's size and ``length_penalty=0`` the result is the sequence with
         the highest summed log-probability, what ``score_continuations(...).sum()`` ranks first.  ``return_logprobs`` stays the model's
-        distribution over the raw logits.  None: nothing is launched or allocated."""
+        distribution over the raw logits.  None: nothing is launched or allocated.
+
+        ``prompt_lookup_num_tokens`` K in 1 .. 7 (with ``max_matching_ngram_size`` G, default 2): speculative greedy decoding by prompt
+        lookup (:mod:`llark_amd.m2t.speculate`) -- every step verifies up to K tokens drafted from the row's own history and keeps those
+        the model would have chosen itself.  Uniform and padded batches both run on the slot mode, B * (K + 1) <= 16.  Plain greedy
+        search only: sampling, a repetition penalty, beams, constraints, ``allowed_continuations``, ``return_logprobs`` and
+        ``share_prefix`` are refused by name.  None or 0: nothing is launched or allocated, the paths above run bit for bit."""
         if num_beam_groups is not None and num_beam_groups != 1:
             raise NotImplementedError(f"num_beam_groups={num_beam_groups!r}: diverse beam groups are not implemented")
+        spec = SpeculationParams.from_generate(
+            prompt_lookup_num_tokens, max_matching_ngram_size, do_sample=bool(do_sample), temperature=temperature not in (None, 1.0),
+            top_k=bool(top_k), top_p=top_p not in (None, 1.0), seed=seed is not None,
+            repetition_penalty=repetition_penalty not in (None, 1.0), num_beams=num_beams not in (None, 1),
+            no_repeat_ngram_size=bool(no_repeat_ngram_size), bad_words_ids=bool(bad_words_ids), suppress_tokens=bool(suppress_tokens),
+            min_new_tokens=bool(min_new_tokens), min_length=bool(min_length), allowed_continuations=allowed_continuations is not None,
+            return_logprobs=bool(return_logprobs), share_prefix=bool(share_prefix))
+        if spec is not None:
+            spec.check_batch(input_ids.shape[0])
+            rows, _, packed = unpack_prompts(input_ids, attention_mask)
+            segs = plan_splice_on(self.engine.device, packed, audio_encodings, self.model.audio_encoder_config)
+            eos = eos_token_id if eos_token_id is not None else getattr(self.generation_config, "eos_token_id", None)
+            pad = getattr(self.generation_config, "pad_token_id", None)
+            pad = eos if pad is None else pad
+            use_eos = eos is not None and eos >= 0
+            return generate_speculative(self.engine, rows, segs, input_ids, *((int(eos), int(pad)) if use_eos else (-1, 0)), max_new_tokens, spec,
+                                        stopping_criteria, drafter=getattr(self, "speculation_drafter", None),
+                                        stats=getattr(self, "speculation_stats", None))
         constraints = constraints_from_generate(no_repeat_ngram_size, bad_words_ids, suppress_tokens, min_new_tokens, min_length)
         guide, choice = guide_from_generate(allowed_continuations, input_ids.shape[0])
         if guide is not None:

@@ -328,6 +328,8 @@ class WrappedMPTForCausalLM(nn.Module):
         allocated."""
         if num_beams is not None and num_beams != 1:
             raise NotImplementedError(f"num_beams={num_beams!r}: beam search is not implemented for MPT (no K/V fork path there yet)")
+        if kwargs.get("prompt_lookup_num_tokens"):
+            raise NotImplementedError("prompt_lookup_num_tokens: speculative decoding is not implemented for MPT (the block attention takes no ALiBi)")
         constraints = constraints_from_generate(no_repeat_ngram_size, bad_words_ids, suppress_tokens, min_new_tokens, min_length)
         guide, choice = guide_from_generate(allowed_continuations, input_ids.shape[0])
         if guide is not None:

@@ -992,6 +992,85 @@ def attn_decode_rope_rows(qkv: torch.Tensor, batch: int, nh: int, hd: int, pos_r
                                                           _opt(alibi_slopes, "alibi_slopes", torch.float32), _stream()), "attn_decode_rope_rows")
 
 
+def attn_decode_rope_block(qkv: torch.Tensor, n_slots: int, stride: int, nh: int, hd: int, blk: torch.Tensor, pos_rows: torch.Tensor, cos_t, sin_t,
+                           k_cache, vt_cache, out, k_cache_lo=None, vt_cache_lo=None, out_lo=None) -> None:
+    """:func:`attn_decode_rope_rows` for ``stride`` rows per slot at consecutive positions (speculative decode step): slot b owns rows
+    ``b*stride .. b*stride + blk[b] - 1``, row i is the token at position ``pos_rows[b] + i``.  ``blk`` / ``pos_rows`` int32 [n_slots] on
+    the device.  Bit-equal to ``blk[b]`` successive :func:`attn_decode_rope_rows` launches; rows that compute nothing get zeros."""
+    smax = k_cache.shape[-2]
+    bf = torch.bfloat16
+    rows = n_slots * stride
+    assert qkv.shape == (rows, 3 * nh * hd) and blk.numel() == n_slots and pos_rows.numel() == n_slots and out.numel() == rows * nh * hd
+    assert k_cache.shape == (n_slots, nh, smax, hd) and vt_cache.shape == (n_slots, nh, hd, smax) and cos_t.shape == sin_t.shape
+    assert out_lo is None or out_lo.shape == out.shape
+    for c in (k_cache_lo, vt_cache_lo):
+        assert c is None or c.shape in (k_cache.shape, vt_cache.shape)
+    with _timed("attn_decode_rope_block", 0.0):
+        check(_lib.lib().llark_attn_decode_rope_bf16_block(_dev(qkv, "qkv", torch.float32), n_slots, stride, nh, hd, _dev(blk, "blk", torch.int32),
+                                                           _dev(pos_rows, "pos_rows", torch.int32), _dev(cos_t, "cos", torch.float32),
+                                                           _dev(sin_t, "sin", torch.float32), cos_t.shape[0], _dev(k_cache, "k_cache", bf),
+                                                           _dev(vt_cache, "vt_cache", bf), _opt(k_cache_lo, "k_cache_lo", bf),
+                                                           _opt(vt_cache_lo, "vt_cache_lo", bf), smax, _dev(out, "out", bf), _opt(out_lo, "out_lo", bf),
+                                                           _stream()), "attn_decode_rope_block")
+
+
+SPEC_MAX_BLOCK = 8            # rows of a block = tokens a slot can emit per step (csrc/speculate.hip)
+
+
+def spec_step_buffer(n_slots: int, device) -> torch.Tensor:
+    """The int64 buffer a block step leaves in ONE transfer: ``[:, :8]`` the emitted tokens, ``[:, 8]`` their count -- as two
+    contiguous regions (``out_tokens`` then ``n_out``), see :func:`spec_step_views`."""
+    return torch.zeros(n_slots * (SPEC_MAX_BLOCK + 1), dtype=torch.int64, device=device)
+
+
+def spec_step_views(buf: torch.Tensor):
+    """``(out_tokens [n_slots][8], n_out [n_slots])`` views of a :func:`spec_step_buffer` (device or host copy)."""
+    n = buf.numel() // (SPEC_MAX_BLOCK + 1)
+    return buf[: n * SPEC_MAX_BLOCK].view(n, SPEC_MAX_BLOCK), buf[n * SPEC_MAX_BLOCK:]
+
+
+def spec_verify_rows(logits: torch.Tensor, ids: torch.Tensor, blk: torch.Tensor, state: torch.Tensor, pos_rows: torch.Tensor, budget: torch.Tensor,
+                     out_tokens: torch.Tensor, n_out: torch.Tensor, next_ids: torch.Tensor, hist: Optional[torch.Tensor] = None,
+                     hist_len: Optional[torch.Tensor] = None, eos: int = -1, pad: int = 0, vocab: Optional[int] = None) -> None:
+    """Greedy verification of a block step in one launch (include/llark_hip.h: llark_spec_verify_rows): per ACTIVE slot the greedy
+    token of every row, the accepted run ``g_0 .. g_a`` cut at ``budget`` and after ``eos``, written to ``out_tokens[b]`` / ``n_out[b]``;
+    ``next_ids``, ``pos_rows``, ``budget``, ``state`` and the device history advance with it."""
+    n_slots = state.numel()
+    i32, i64 = torch.int32, torch.int64
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] % n_slots == 0
+    stride = logits.shape[0] // n_slots
+    vocab = logits.shape[1] if vocab is None else vocab
+    assert 0 < vocab <= logits.shape[1] and ids.numel() == n_slots * stride
+    assert blk.numel() == pos_rows.numel() == budget.numel() == next_ids.numel() == n_out.numel() == n_slots
+    assert out_tokens.shape == (n_slots, SPEC_MAX_BLOCK) and (hist is None) == (hist_len is None)
+    assert hist is None or (hist.dim() == 2 and hist.shape[0] == n_slots and hist_len.numel() == n_slots)
+    check(_lib.lib().llark_spec_verify_rows(_dev(logits, "logits", torch.float32, contiguous=False), logits.stride(0), int(vocab), n_slots, stride,
+                                            _dev(ids, "ids", i64), _dev(blk, "blk", i32), _dev(state, "state", i32),
+                                            _dev(pos_rows, "pos_rows", i32), _dev(budget, "budget", i32), int(eos), int(pad),
+                                            _dev(out_tokens, "out_tokens", i64), _dev(n_out, "n_out", i64), _dev(next_ids, "next_ids", i64),
+                                            _opt(hist, "hist", i64), _opt(hist_len, "hist_len", i32), 0 if hist is None else hist.shape[1],
+                                            _stream()), "spec_verify_rows")
+
+
+def spec_draft_rows(next_ids: torch.Tensor, state: torch.Tensor, pos_rows: torch.Tensor, budget: torch.Tensor, ids: torch.Tensor, blk: torch.Tensor,
+                    stride: int, k_max: int, smax: int, hist: Optional[torch.Tensor] = None, hist_len: Optional[torch.Tensor] = None,
+                    g_max: int = 2, drafts: Optional[torch.Tensor] = None, n_drafts: Optional[torch.Tensor] = None, pad: int = 0) -> None:
+    """Fills the next block in one launch (include/llark_hip.h: llark_spec_draft_rows): row 0 of slot b is ``next_ids[b]``, then up to
+    ``k_max`` drafts -- ``drafts[b, :n_drafts[b]]`` when given, else the prompt lookup over ``hist`` (suffixes of ``g_max`` down to 1
+    tokens) -- and ``blk[b] = 1 + n_draft``, capped by ``stride``, ``budget`` and ``smax``."""
+    n_slots = state.numel()
+    i32, i64 = torch.int32, torch.int64
+    assert ids.numel() == n_slots * stride and blk.numel() == pos_rows.numel() == budget.numel() == next_ids.numel() == n_slots
+    assert (drafts is None) == (n_drafts is None) and (hist is None) == (hist_len is None) and (drafts is not None or hist is not None)
+    assert drafts is None or (drafts.dim() == 2 and drafts.shape[0] == n_slots and n_drafts.numel() == n_slots)
+    assert hist is None or (hist.dim() == 2 and hist.shape[0] == n_slots and hist_len.numel() == n_slots)
+    check(_lib.lib().llark_spec_draft_rows(_dev(next_ids, "next_ids", i64), _dev(state, "state", i32), _dev(pos_rows, "pos_rows", i32),
+                                           _dev(budget, "budget", i32), _opt(hist, "hist", i64), _opt(hist_len, "hist_len", i32),
+                                           0 if hist is None else hist.shape[1], n_slots, int(stride), int(k_max), int(g_max), int(smax),
+                                           _opt(drafts, "drafts", i64), _opt(n_drafts, "n_drafts", i32), 0 if drafts is None else drafts.shape[1],
+                                           _dev(ids, "ids", i64), _dev(blk, "blk", i32), int(pad), _stream()), "spec_draft_rows")
+
+
 def mpt_attn_decode_rows(qkv: torch.Tensor, batch: int, nh: int, hd: int, pos_rows: torch.Tensor, clip_qkv, q_ln_w, q_ln_b, k_ln_w, k_ln_b,
                          ln_eps: float, k_cache, vt_cache, out, k_cache_lo=None, vt_cache_lo=None, out_lo=None, alibi_slopes=None) -> None:
     """MPT ragged decode front + attention in one launch: clamp (``clip_qkv`` None / 0: none), qk_ln (``q_ln_w`` None: none), head split,
